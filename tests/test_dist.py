@@ -114,7 +114,11 @@ def _run_world(tmpdir, nproc=2):
     env["SEA_REPO"] = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env["SEA_OUT"] = outfile
     env["MASTER_ADDR"] = "127.0.0.1"
-    env.pop("HIP_VISIBLE_DEVICES", None)
+    # gloo/CPU worlds: hide the GPUs from the workers, otherwise on a GPU
+    # host every rank binds cuda:<local_rank> and ranks past the device
+    # count die (a 2-rank world on a 1-GPU machine)
+    env["HIP_VISIBLE_DEVICES"] = "-1"
+    env["CUDA_VISIBLE_DEVICES"] = "-1"
     import random
 
     last = None

@@ -28,7 +28,11 @@ def _env(tmpdir, trace_name=None, port="29881"):
     env = dict(os.environ)
     env["SEA_REPO"] = REPO
     env["MASTER_ADDR"] = "127.0.0.1"
-    env.pop("HIP_VISIBLE_DEVICES", None)
+    # gloo/CPU worlds: hide the GPUs from the workers, otherwise on a GPU
+    # host every rank binds cuda:<local_rank> (and picks RCCL) and ranks
+    # past the device count die
+    env["HIP_VISIBLE_DEVICES"] = "-1"
+    env["CUDA_VISIBLE_DEVICES"] = "-1"
     if trace_name:
         env["SEA_COMM_TRACE"] = os.path.join(tmpdir, trace_name)
     return env

@@ -144,8 +144,32 @@ def test_grow_tree_delegation_forall(n, f, b, depth, weighted, masked, seed):
     c = _grow_tree_seq(bins, edges, grad, hess, params, row_mask=mask)
     for k in ("feature", "threshold", "left_child"):
         assert torch.equal(a[k].float(), c[k].float()), k
-    assert torch.allclose(a["leaf_value"], c["leaf_value"],
-                          rtol=1e-4, atol=2e-5)
+    # Leaf values are G_leaf / H_leaf with f32 (G, H) totals that each
+    # grower derives top-down as parent - sibling, in its own summation
+    # order.  Every level adds a rounding error of up to one f32 ulp of the
+    # ROOT-sized totals to both G and H, so a light leaf under a heavy root
+    # carries (|dG| + |v| |dH|) / H_leaf on top of the plain rtol/atol,
+    # with dG, dH <= 2 (depth + 1) eps32 * (sum|g|, sum h) per grower.
+    # A single misplaced row would move a leaf by ~|g| / H_leaf, hundreds
+    # of times this allowance.
+    rows = (mask.nonzero(as_tuple=True)[0] if mask is not None
+            else torch.arange(n))
+    n_nodes = a["feature"].numel()
+    leaf_of = reference.tree_predict(
+        x[rows], a["feature"], a["threshold"], a["left_child"],
+        torch.arange(n_nodes, dtype=torch.float32).unsqueeze(1), depth,
+    ).reshape(-1).long()
+    h_leaf = torch.zeros(n_nodes, dtype=torch.float64).index_add_(
+        0, leaf_of, hess[rows].double())
+    eps32 = float(torch.finfo(torch.float32).eps)
+    slack = 2 * 2 * (depth + 1) * eps32  # two growers
+    d_g = slack * float(grad[rows].abs().sum())
+    d_h = slack * float(hess[rows].sum())
+    va, vc = a["leaf_value"].double().reshape(-1), c["leaf_value"].double().reshape(-1)
+    allowed = (2e-5 + 1e-4 * vc.abs()
+               + (d_g + vc.abs() * d_h) / h_leaf.clamp_min(0.5))
+    assert bool(((va - vc).abs() <= allowed).all()), \
+        float(((va - vc).abs() - allowed).max())
 
 
 @settings(max_examples=8, deadline=None)
