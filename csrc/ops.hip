@@ -42,9 +42,9 @@ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // fetch) before the slot is touched again.
 static torch::Tensor h2d_async(const void* src, size_t bytes, int slot,
                                const torch::Device& dev) {
-  static thread_local torch::Tensor pin[16];
-  static thread_local hipEvent_t done[16] = {};
-  static thread_local unsigned char flip[8] = {};
+  static thread_local torch::Tensor pin[24];
+  static thread_local hipEvent_t done[24] = {};
+  static thread_local unsigned char flip[12] = {};
   // the PREVIOUS copy from this slot may still be pending on the
   // stream: overwriting (or freeing, when the slot grows) the pinned
   // staging before the DMA reads it feeds the kernels garbage
@@ -76,6 +76,12 @@ static torch::Tensor h2d_async(const void* src, size_t bytes, int slot,
     (void)hipEventCreateWithFlags(&done[bi], hipEventDisableTiming);
   (void)hipEventRecord(done[bi], stream);
   return d;
+}
+
+// csrc/wide_class.hip shares the staging (slots 8-9 are its own)
+torch::Tensor sea_h2d_async(const void* src, size_t bytes, int slot,
+                            const torch::Device& dev) {
+  return h2d_async(src, bytes, slot, dev);
 }
 
 // ---------------------------------------------------------------------------
@@ -1686,6 +1692,13 @@ __global__ void split_decode_kernel(
   if (threadIdx.x < C) left_stats[node * C + threadIdx.x] = acc[threadIdx.x];
 }
 
+// csrc/wide_class.hip: one wave per (node, feature), channel loop in LDS
+void split_argmax_wide(torch::Tensor gain, torch::Tensor feat,
+                       torch::Tensor bin, torch::Tensor left_stats,
+                       torch::Tensor hist, int D, double lam,
+                       double min_child_weight, double min_instances,
+                       double min_info_gain);
+
 void split_argmax(torch::Tensor gain, torch::Tensor feat, torch::Tensor bin,
                   torch::Tensor left_stats, torch::Tensor hist, int64_t d_dims,
                   double lam, double min_child_weight, double min_instances,
@@ -1696,9 +1709,16 @@ void split_argmax(torch::Tensor gain, torch::Tensor feat, torch::Tensor bin,
   const int B = (int)hist.size(2);
   const int C = (int)hist.size(3);
   const int D = d_dims > 0 ? (int)d_dims : C - 2;
-  TORCH_CHECK(C >= 2 && C <= 8, "split_argmax: 2 <= C <= 8");
+  TORCH_CHECK(C >= 2 && C <= 34, "split_argmax: 2 <= C <= 34");
   TORCH_CHECK(B >= 2 && B <= 256, "split_argmax: 2 <= B <= 256");
   TORCH_CHECK(D >= 1 && D < C, "split_argmax: bad D");
+  if (C > 8) {
+    // wide one-hot channels (gini trees with 7..32 classes)
+    CHECK_GPU(gain); CHECK_GPU(feat); CHECK_GPU(bin); CHECK_GPU(left_stats);
+    split_argmax_wide(gain, feat, bin, left_stats, hist, D, lam,
+                      min_child_weight, min_instances, min_info_gain);
+    return;
+  }
   auto best = torch::zeros({n}, hist.options().dtype(torch::kInt64));
   auto stream = at::hip::getCurrentHIPStream();
   const int fpb = 4;  // features (waves) per block
@@ -1733,6 +1753,14 @@ void logreg_loss_grad(torch::Tensor payload, torch::Tensor x, torch::Tensor y,
                       torch::Tensor w, torch::Tensor wmat, bool has_bias);
 bool logreg_fused_supported(int64_t F, int64_t K);
 
+// csrc/wide_class.hip
+int64_t hist_build_class(torch::Tensor out, torch::Tensor bins,
+                         torch::Tensor bins_t, torch::Tensor label,
+                         torch::Tensor weight, torch::Tensor row_idx,
+                         torch::Tensor node_offsets, torch::Tensor node_col0,
+                         int64_t num_bins, int64_t num_classes, int64_t nn,
+                         double w_max, bool identity_rows);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("logreg_loss_grad", &logreg_loss_grad,
         "single-pass fused logistic loss+gradient");
@@ -1742,6 +1770,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_weights", &sample_weights, "counter-based Poisson/Bernoulli row weights");
   m.def("bin_features", &bin_features, "quantile binning f32 -> u8");
   m.def("hist_build", &hist_build, "LDS-staged node histograms");
+  m.def("hist_build_class", &hist_build_class,
+        "label-indexed node histograms for K-class gini trees");
   m.def("partition_rows", &partition_rows, "block-aggregated node partition");
   m.def("tree_predict", &tree_predict, "single-tree batched predict");
   m.def("forest_predict", &forest_predict, "packed-forest weighted predict");

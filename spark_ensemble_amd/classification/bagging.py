@@ -76,12 +76,16 @@ class BaggingClassifier(ProbabilisticClassifier, _BaggingClassifierParams):
             subspace(self.getSubspaceRatio(), num_features, seed + i) for i in range(k)
         ]
 
-        from ..models.tree import DecisionTreeClassifier, fit_class_tree_forest
+        from ..models.tree import (
+            DecisionTreeClassifier, _class_mode_ok, fit_class_tree_forest,
+        )
 
+        # 7..32 classes fuse too on the GPU (the grower's class mode)
+        wide_fused = x.is_cuda and _class_mode_ok(num_classes)
         if (
             type(learner) is DecisionTreeClassifier
             and learner.getOrDefault("minWeightFractionPerNode") == 0.0
-            and num_classes + 2 <= 8
+            and (num_classes + 2 <= 8 or wide_fused)
         ):
             # fused path: all k gini trees (K one-hot channels each) grow
             # level-synchronously; subspaces as split masks, bags as root
@@ -98,12 +102,14 @@ class BaggingClassifier(ProbabilisticClassifier, _BaggingClassifierParams):
                 (bag_w[:, i] > 0).nonzero(as_tuple=True)[0].to(torch.int32)
                 for i in range(k)
             ]
-            onehot = torch.zeros(n, num_classes, dtype=torch.float32,
-                                 device=x.device)
-            onehot.scatter_(1, y.long().unsqueeze(1), 1.0)
+            onehot = None
+            if not wide_fused:  # class mode reads the labels directly
+                onehot = torch.zeros(n, num_classes, dtype=torch.float32,
+                                     device=x.device)
+                onehot.scatter_(1, y.long().unsqueeze(1), 1.0)
             models = fit_class_tree_forest(
                 learner, f_edges, f_bins, onehot, bag_w, num_classes, comm,
-                subspaces=subspaces, root_rows=root_rows,
+                subspaces=subspaces, root_rows=root_rows, labels=y,
             )
             model = BaggingClassificationModel()
             model._models = models

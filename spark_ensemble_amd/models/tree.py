@@ -345,20 +345,37 @@ def fit_tree_forest(learner, edges, bins, labels, weights, comm=None,
     return models, tp_out[0]
 
 
+def _class_mode_ok(k_classes: int) -> bool:
+    """Class counts served by the arena grower's class mode on the GPU
+    (K <= 6 fits the generic 8-channel kernels; K > 32 exceeds the
+    label-indexed histogram's LDS layout and keeps the loop grower)."""
+    return 7 <= int(k_classes) <= 32
+
+
 def fit_class_tree_forest(learner, edges, bins, onehot, weights, k_classes,
-                          comm=None, subspaces=None, root_rows=None):
+                          comm=None, subspaces=None, root_rows=None,
+                          labels=None):
     """T independent ``DecisionTreeClassifier`` fits (gini trees, D = K
-    one-hot channels) as fused forest grows.  ``onehot`` [N, K];
-    ``weights`` [N, T] per-tree bag weights (positive on each tree's
-    ``root_rows``).  K + 2 channels per tree must fit the kernel's
-    8-channel cap (K <= 6 with non-unit weights).  Members are chunked so
-    the [N, chunk, K] gradient tensor stays modest."""
+    one-hot channels) as fused forest grows.  ``weights`` [N, T] per-tree
+    bag weights (positive on each tree's ``root_rows``).
+
+    Two routes, by K and device:
+
+    * K <= 6 (any device): ``onehot`` [N, K] x weights become the
+      [N, chunk, K] gradient tensor of the generic grower — K + 2 channels
+      per tree must fit its 8-channel cap — and members are chunked so
+      that tensor stays modest.
+    * 7 <= K <= 32 on CUDA tensors: the grower's class mode.  Only
+      ``labels`` [N] (class ids; derived from ``onehot`` when omitted, and
+      ``onehot`` may then be None) and the weights are read, no gradient
+      tensor exists, and ``grow_forest`` itself batches the members by the
+      level-histogram size."""
     from ..parallel import get_comm as _gc
     from .tree_grower import grow_forest
 
     comm = comm or _gc()
     F = bins.shape[1]
-    N, K = onehot.shape
+    K = int(k_classes)
     T = weights.shape[1]
     gp = learner._grow_params(1.0)
     stats = torch.stack([weights.abs().max()])
@@ -366,13 +383,18 @@ def fit_class_tree_forest(learner, edges, bins, onehot, weights, k_classes,
         comm.all_reduce_(stats, "max")
     hmax = float(stats.cpu()[0])
     gh_max = torch.tensor([max(hmax, 1.0)] * K + [hmax, 1.0])
+    class_mode = bins.is_cuda and _class_mode_ok(K)
+    if class_mode and labels is None:
+        labels = onehot.argmax(dim=1)
 
     models = []
-    chunk = max(2, 16 // max(K // 3, 1))
+    chunk = T if class_mode else max(2, 16 // max(K // 3, 1))
     for s in range(0, T, chunk):
         sl = slice(s, min(s + chunk, T))
         w_sl = weights[:, sl]
-        grads = (onehot.unsqueeze(1) * w_sl.unsqueeze(2)).contiguous()
+        grads = None
+        if not class_mode:
+            grads = (onehot.unsqueeze(1) * w_sl.unsqueeze(2)).contiguous()
         fmasks = None
         subs_sl = subspaces[sl] if subspaces is not None else None
         if subs_sl is not None and any(x.numel() != F for x in subs_sl):
@@ -385,6 +407,8 @@ def fit_class_tree_forest(learner, edges, bins, onehot, weights, k_classes,
             hess_is_count=False, gh_max_in=gh_max,
             root_rows=root_rows[sl] if root_rows is not None else None,
             feature_masks=fmasks,
+            class_labels=labels if class_mode else None,
+            num_classes=K if class_mode else 0,
         )
         for t, tree in enumerate(trees):
             nf = F
@@ -412,6 +436,13 @@ class DecisionTreeClassifier(ProbabilisticClassifier, _TreeParams):
         comm = get_comm()
         k = int(comm.all_reduce_scalar(k, "max"))
         edges, bins = ensure_binned(dataset, x, self.getOrDefault("maxBins"))
+        if x.is_cuda and _class_mode_ok(k):
+            tree = self._grow_class_mode(bins, edges, y, w, k, comm)
+            model = DecisionTreeClassificationModel()
+            model._set_tree(tree, x.shape[1])
+            model._num_classes = k
+            model._copy_cols_from(self)
+            return model
         onehot = torch.zeros(x.shape[0], k, dtype=torch.float32, device=x.device)
         onehot.scatter_(1, y.long().unsqueeze(1), 1.0)
         grad = onehot * w.unsqueeze(1)
@@ -427,6 +458,34 @@ class DecisionTreeClassifier(ProbabilisticClassifier, _TreeParams):
         model._num_classes = k
         model._copy_cols_from(self)
         return model
+
+    def _grow_class_mode(self, bins, edges, y, w, k, comm):
+        """7 <= K <= 32 on the GPU: the arena grower's class mode (label-
+        indexed histograms + wide split kernel) instead of the per-node
+        loop grower; no [N, K] one-hot matrix is built."""
+        from .tree_grower import grow_forest
+
+        sums = torch.stack([
+            w.sum(),
+            (w == 0).sum().to(torch.float32),
+            (w != 1).sum().to(torch.float32),
+        ])
+        maxs = w.abs().amax().reshape(1) if w.numel() else w.new_zeros(1)
+        if comm.is_distributed:
+            comm.all_reduce_(sums)
+            comm.all_reduce_(maxs, "max")
+        sums_c = torch.cat([sums, maxs]).cpu()  # one host sync
+        total_w, has_zero = float(sums_c[0]), float(sums_c[1]) > 0
+        all_one = float(sums_c[2]) == 0
+        gp = self._grow_params(total_w)
+        root_rows = None
+        if has_zero:
+            root_rows = [(w > 0).nonzero(as_tuple=True)[0].to(torch.int32)]
+        return grow_forest(
+            bins, edges, None, w, gp, comm, hess_is_count=all_one,
+            gh_max_in=sums_c[3:4], root_rows=root_rows,
+            class_labels=y.to(torch.uint8), num_classes=k,
+        )[0]
 
 
 class DecisionTreeClassificationModel(

@@ -196,12 +196,66 @@ def hist_build_forest(bins, gh, row_idx, node_offsets, node_col0, num_bins,
     )
 
 
+# what the last GPU hist_build_class launch did (tests assert the
+# multi-chunk staging path was taken without guessing the chunk policy)
+last_hist_build_class_info: dict = {}
+
+
+def hist_build_class(bins, label, weight, row_idx, node_offsets, node_col0,
+                     num_bins, num_classes, nn, w_max=None,
+                     identity_rows=False, transposed=None):
+    """Label-indexed histograms for K-class gini trees (2 <= K <= 32).
+
+    ``label`` [N] u8, ``weight`` [N, T] f32 >= 0 (one column per fused
+    tree), host ``node_offsets`` / ``node_col0`` (per-node weight column).
+    Output [n_nodes, F, B, K + nn] in the grower's layout (classes, hess,
+    count when nn == 2).  The gfx950 kernel spends ONE ds_add_u64 per
+    (row, feature) and quantises with a power-of-two scale sized by the
+    host scalar ``w_max`` (computed here, with one sync, when None), so
+    integer-valued weights histogram exactly.  ``transposed`` picks the
+    bins source: the cached [F, N] transpose (default, see
+    profiles/wide_class.md) or the row-major matrix.
+    """
+    if bins.is_cuda:
+        m = _require_hip("hist_build_class")
+        if m is not None:
+            n_nodes = node_offsets.numel() - 1
+            F = bins.shape[1]
+            C = int(num_classes) + int(nn)
+            if w_max is None:
+                w_max = float(weight.max()) if weight.numel() else 1.0
+            if transposed is None:
+                transposed = os.environ.get("SEA_CLASS_HIST_SRC") != "rowmajor"
+            bt = _bins_transposed(bins) if transposed else _EMPTY_U8
+            # every node's slice is fully written by the flush or the
+            # decode pass (zero-row nodes included) — no zero fill
+            out = torch.empty(n_nodes, F, num_bins, C, dtype=torch.float32,
+                              device=bins.device)
+            n_multi = m.hist_build_class(
+                out, bins, bt, label, weight.contiguous(),
+                row_idx.to(torch.int32),
+                node_offsets.to(torch.int64).cpu(),
+                node_col0.to(torch.int32).cpu().contiguous(),
+                int(num_bins), int(num_classes), int(nn), float(w_max),
+                bool(identity_rows),
+            )
+            last_hist_build_class_info["multi_chunk_nodes"] = int(n_multi)
+            return out
+    return reference.hist_build_class(
+        bins, label, weight, row_idx, node_offsets, node_col0, num_bins,
+        num_classes, nn,
+    )
+
+
+SPLIT_WIDE_MAX_C = 34  # K <= 32 one-hot channels + hess + count
+
+
 def split_search(hist, lam=1e-6, min_child_weight=0.0, min_instances=1.0, min_info_gain=0.0, d_dims=-1):
     if hist.is_cuda:
         c_chk = hist.shape[3]
-        if c_chk > 8:
-            # wide one-hot channels (K > 7 gini trees): eager torch path
-            # (runs on GPU; the fused kernel caps at 8 channels)
+        if c_chk > SPLIT_WIDE_MAX_C:
+            # beyond the wide kernel's channel cap (K > 32 gini trees):
+            # eager torch path (runs on GPU)
             return reference.split_search(
                 hist, lam, min_child_weight, min_instances, min_info_gain,
                 d_dims,

@@ -171,6 +171,45 @@ def hist_build_forest(bins, gh, row_idx, node_offsets, node_col0, num_bins,
     return out
 
 
+def hist_build_class(bins, label, weight, row_idx, node_offsets, node_col0,
+                     num_bins, num_classes, nn, w_max=None):
+    """Label-indexed histograms for K-class gini trees.
+
+    ``label`` [N] u8 in [0, K), ``weight`` [N, T] f32 >= 0; node nd sums
+    weight column ``node_col0[nd]`` (its owning tree).  Returns
+    [n_nodes, F, num_bins, K + nn] f32 in the grower's layout: channels
+    [0, K) per-class weight sums, channel K the hessian (weight sum over all
+    classes), channel K + 1 (nn == 2) the row count — what ``hist_build``
+    gives for the one-hot x weight gradient matrix, without building it.
+    ``w_max`` only sizes the GPU kernel's quantisation; unused here.
+    """
+    n_nodes = node_offsets.numel() - 1
+    N, F = bins.shape
+    K = int(num_classes)
+    C = K + int(nn)
+    dev = bins.device
+    out = torch.zeros(n_nodes, F, num_bins, C, dtype=torch.float32, device=dev)
+    offs = node_offsets.tolist()
+    col0s = node_col0.tolist()
+    fb = torch.arange(F, device=dev, dtype=torch.long) * num_bins
+    for nd in range(n_nodes):
+        s, e = offs[nd], offs[nd + 1]
+        if e <= s:
+            continue
+        rows = row_idx[s:e].long()
+        cell = bins.index_select(0, rows).long() + fb.unsqueeze(0)  # [m, F]
+        lab = label.index_select(0, rows).long().unsqueeze(1)  # [m, 1]
+        w = weight[:, int(col0s[nd])].index_select(0, rows)
+        flat = out[nd].reshape(F * num_bins * C)  # view: rows of C channels
+        wf = w.unsqueeze(1).expand(-1, F).reshape(-1)
+        base = (cell * C).reshape(-1)
+        flat.index_add_(0, (cell * C + lab).reshape(-1), wf)
+        flat.index_add_(0, base + K, wf)
+        if nn == 2:
+            flat.index_add_(0, base + K + 1, torch.ones_like(wf))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # Split search (vectorized over nodes x features x bins; works on both
 # devices as plain tensor algebra — small relative to hist_build)

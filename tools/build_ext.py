@@ -19,6 +19,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = [
     os.path.join(REPO, "csrc", "ops.hip"),
     os.path.join(REPO, "csrc", "linear.hip"),
+    os.path.join(REPO, "csrc", "wide_class.hip"),
 ]
 OUT = os.path.join(REPO, "spark_ensemble_amd", "_hip_ops.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
