@@ -1196,7 +1196,9 @@ __device__ inline float scalar_loss_grad(int loss_id, float param, float y,
     }
     case L_ABSOLUTE: {
       float d = y - p;
-      *grad = -copysignf(1.0f, d);
+      // -sign(d) with sign(+-0) = 0, as losses.py (torch.sign) and the
+      // reference (math.signum): an exact tie has pseudo-residual 0
+      *grad = (d > 0.0f) ? -1.0f : ((d < 0.0f) ? 1.0f : 0.0f);
       *hess = 0.0f;
       return fabsf(d);
     }
@@ -1234,8 +1236,11 @@ __device__ inline float scalar_loss_grad(int loss_id, float param, float y,
       return (d > 0.0f) ? param * d : (param - 1.0f) * d;
     }
     case L_EXPONENTIAL: {
-      // y in {-1, 1}
-      float e = __expf(-y * p);
+      // y in {-1, 1}.  expf, not __expf: the loss IS the exponential, so
+      // the fast form's relative error (~|y p| * 2^-24 from rounding
+      // y p * log2(e)) reaches loss, gradient and hessian undamped, about
+      // 5e-6 at |y p| = 80 (profiles/loss_kernels.md)
+      float e = expf(-y * p);
       *grad = -y * e;
       *hess = e;  // y^2 = 1
       return e;

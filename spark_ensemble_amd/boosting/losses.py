@@ -23,7 +23,7 @@ from typing import Optional
 
 import torch
 
-# loss ids shared with the HIP kernels (csrc/gbm_losses.hip)
+# loss ids shared with the HIP kernels (csrc/ops.hip)
 LOSS_IDS = {
     "squared": 0,
     "absolute": 1,
