@@ -1,0 +1,70 @@
+// Shared by csrc/ops.hip, csrc/linear.hip and csrc/wide_class.hip: argument
+// checks, the pinned upload helper with its slot table, the sortable-float
+// encoding of the split scans, and the entry points that cross files.
+#pragma once
+
+#include <torch/extension.h>
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#define CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be on GPU")
+#define CHECK_CONTIG(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
+
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// order-preserving f32 <-> u32 (packed atomicMax split search)
+__device__ inline unsigned f32_sortable(float f) {
+  unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ inline float sortable_f32(unsigned s) {
+  unsigned u = (s & 0x80000000u) ? (s & 0x7FFFFFFFu) : ~s;
+  return __uint_as_float(u);
+}
+
+// Pinned ping-pong staging slots of h2d_async, one name per call site.
+// gather_ranges and leaf_scatter share a slot; every other site owns its.
+enum UploadSlot : int {
+  kSlotHistChunks = 0,      // hist_build: scales + chunk table
+  kSlotHistNodes = 1,       // hist_build: staging slot -> node
+  kSlotPartCursors = 2,     // partition_rows: per-node cursors
+  kSlotPartChunks = 3,      // partition_rows: chunk table
+  kSlotPartSegStart = 4,    // partition_rows: segment starts
+  kSlotGatherSegs = 5,      // gather_ranges: prefix + starts
+  kSlotLeafSegs = kSlotGatherSegs,  // leaf_scatter: prefix + starts
+  kSlotLeafTree = 6,        // leaf_scatter: tree ids
+  kSlotLeafVal = 7,         // leaf_scatter: leaf values
+  kSlotClassChunks = 8,     // hist_build_class: scale + chunk table
+  kSlotClassNodes = 9,      // hist_build_class: slot -> node + scales
+  kUploadSlots = 12,
+};
+
+// csrc/ops.hip: async H2D of a small host table through pinned staging
+torch::Tensor h2d_async(const void* src, size_t bytes, UploadSlot slot,
+                        const torch::Device& dev);
+
+// csrc/ops.hip: decode the i64 staging sums of multi-chunk nodes into f32,
+// out[nodes[slot]] = stage[slot] / scales[channel]; nodes and scales are
+// device pointers
+void launch_hist_decode(float* out, const long long* stage, const int* nodes,
+                        const float* scales, int n_multi, int64_t FBC, int C,
+                        hipStream_t stream);
+
+// csrc/wide_class.hip
+void split_argmax_wide(torch::Tensor gain, torch::Tensor feat,
+                       torch::Tensor bin, torch::Tensor left_stats,
+                       torch::Tensor hist, int D, double lam,
+                       double min_child_weight, double min_instances,
+                       double min_info_gain);
+int64_t hist_build_class(torch::Tensor out, torch::Tensor bins,
+                         torch::Tensor bins_t, torch::Tensor label,
+                         torch::Tensor weight, torch::Tensor row_idx,
+                         torch::Tensor node_offsets, torch::Tensor node_col0,
+                         int64_t num_bins, int64_t num_classes, int64_t nn,
+                         double w_max, bool identity_rows);
+
+// csrc/linear.hip
+void logreg_loss_grad(torch::Tensor payload, torch::Tensor x, torch::Tensor y,
+                      torch::Tensor w, torch::Tensor wmat, bool has_bias);
+bool logreg_fused_supported(int64_t F, int64_t K);

@@ -24,18 +24,11 @@
 //   shfl_xor-reduced, gradient accumulates in registers and is flushed
 //   once per wave via global f32 atomics (-munsafe-fp-atomics).
 
-#include <hip/hip_runtime.h>
-#include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include <cstdint>
-
-#define L_CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be on GPU")
-#define L_CHECK_CONTIG(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
+#include "common.h"
 
 namespace {
-
-inline int64_t lceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // NC = number of 256-feature chunks (F <= NC*256), K = classes.
 // WREG: cache each lane's OWN weight slice in registers — lane l only
@@ -213,8 +206,8 @@ template <int NC, int K>
 void launch_logreg(float* payload, const float* x, const int* y,
                    const float* w, const float* wmat, int64_t n, int F,
                    int has_bias, hipStream_t stream) {
-  const int64_t waves_needed = lceil_div(n, 16);  // >=16 rows per wave
-  int blocks = (int)std::min<int64_t>(lceil_div(waves_needed, 4), 4096);
+  const int64_t waves_needed = ceil_div(n, 16);  // >=16 rows per wave
+  int blocks = (int)std::min<int64_t>(ceil_div(waves_needed, 4), 4096);
   blocks = std::max(blocks, 1);
   // measured (gpurun_out/r02_logreg.json): W-in-LDS 3.1 TB/s vs
   // W-in-registers 2.86 TB/s at 5M x 1024 K=2 — the LDS reads hide
@@ -261,16 +254,16 @@ void launch_logreg(float* payload, const float* x, const int* y,
 // Returns true if this (F, K) combination is supported by the fused kernel.
 bool logreg_fused_supported(int64_t F, int64_t K) {
   if (K < 2 || K > 8) return false;
-  const int64_t nc = lceil_div(F, 256);
+  const int64_t nc = ceil_div(F, 256);
   return nc >= 1 && nc * 4 * K <= 64;  // register-budget cap
 }
 
 void logreg_loss_grad(torch::Tensor payload, torch::Tensor x, torch::Tensor y,
                       torch::Tensor w, torch::Tensor wmat, bool has_bias) {
-  L_CHECK_GPU(payload); L_CHECK_GPU(x); L_CHECK_GPU(y); L_CHECK_GPU(w);
-  L_CHECK_GPU(wmat);
-  L_CHECK_CONTIG(payload); L_CHECK_CONTIG(x); L_CHECK_CONTIG(y);
-  L_CHECK_CONTIG(w); L_CHECK_CONTIG(wmat);
+  CHECK_GPU(payload); CHECK_GPU(x); CHECK_GPU(y); CHECK_GPU(w);
+  CHECK_GPU(wmat);
+  CHECK_CONTIG(payload); CHECK_CONTIG(x); CHECK_CONTIG(y);
+  CHECK_CONTIG(w); CHECK_CONTIG(wmat);
   const int64_t n = x.size(0);
   const int F = (int)x.size(1);
   const int K = (int)wmat.size(1);
@@ -280,7 +273,7 @@ void logreg_loss_grad(torch::Tensor payload, torch::Tensor x, torch::Tensor y,
               "unsupported (F, K) for fused logreg: ", F, ", ", K);
   TORCH_CHECK(y.scalar_type() == torch::kInt, "y must be int32");
   auto stream = at::hip::getCurrentHIPStream();
-  const int nc = (int)lceil_div(F, 256);
+  const int nc = (int)ceil_div(F, 256);
 #define LR_LAUNCH(NCC, KK)                                                   \
   launch_logreg<NCC, KK>(payload.data_ptr<float>(), x.data_ptr<float>(),     \
                          y.data_ptr<int>(), w.data_ptr<float>(),             \

@@ -15,23 +15,19 @@
 //                       shard + one short reduction payload)
 //
 // Design notes (MI355X_MICROARCH.md): 64-wide waves, 256-thread blocks;
-// histograms live in LDS (dynamic, <= 48 KiB keeps 3 blocks/CU resident);
-// chunk sizes are chosen host-side so the grid is ~2-3x the resident block
-// capacity (minimizes the global-atomic flush that dominated the naive
-// version); single-chunk nodes flush with plain stores.
+// histograms live in LDS; the host cuts each level into chunks sized to the
+// resident grid (policy in csrc/hist_plan.h, shared with wide_class.hip);
+// single-chunk nodes flush with plain stores.
 
-#include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include <hip/hip_runtime.h>
 
 #include <chrono>
 #include <cstring>
+#include <tuple>
 #include <vector>
 
-#define CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be on GPU")
-#define CHECK_CONTIG(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
-
-static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+#include "common.h"
+#include "hist_plan.h"
 
 // Persistent pinned staging for the small per-launch host tables (chunk
 // lists, cursors): a pageable .to(device) blocks the HOST until the copy
@@ -40,11 +36,11 @@ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // non_blocking copy keeps the host running ahead.  Slots rotate per call
 // site; reuse is safe because every level ends in a host sync (the split
 // fetch) before the slot is touched again.
-static torch::Tensor h2d_async(const void* src, size_t bytes, int slot,
-                               const torch::Device& dev) {
-  static thread_local torch::Tensor pin[24];
-  static thread_local hipEvent_t done[24] = {};
-  static thread_local unsigned char flip[12] = {};
+torch::Tensor h2d_async(const void* src, size_t bytes, UploadSlot slot,
+                        const torch::Device& dev) {
+  static thread_local torch::Tensor pin[2 * kUploadSlots];
+  static thread_local hipEvent_t done[2 * kUploadSlots] = {};
+  static thread_local unsigned char flip[kUploadSlots] = {};
   // the PREVIOUS copy from this slot may still be pending on the
   // stream: overwriting (or freeing, when the slot grows) the pinned
   // staging before the DMA reads it feeds the kernels garbage
@@ -76,12 +72,6 @@ static torch::Tensor h2d_async(const void* src, size_t bytes, int slot,
     (void)hipEventCreateWithFlags(&done[bi], hipEventDisableTiming);
   (void)hipEventRecord(done[bi], stream);
   return d;
-}
-
-// csrc/wide_class.hip shares the staging (slots 8-9 are its own)
-torch::Tensor sea_h2d_async(const void* src, size_t bytes, int slot,
-                            const torch::Device& dev) {
-  return h2d_async(src, bytes, slot, dev);
 }
 
 // ---------------------------------------------------------------------------
@@ -240,22 +230,23 @@ void bin_features(torch::Tensor out, torch::Tensor x, torch::Tensor edges) {
 //   |sum| < 2^30 per chunk per bin (no field overflow, low->high carries
 //   impossible since low fields are non-negative and bounded).
 //
-//   chunks: int32 [n_chunks, 5] = (node, start, len, single_chunk_flag,
-//   col0); quantization scales ride in the same upload (one H2D per
-//   launch).  ``col0`` is the node's base column in a gh matrix of row
+//   chunks: int32 [n_chunks, 5] = (node, start, len, stage_slot, col0)
+//   as planned by csrc/hist_plan.h; quantization scales ride in the same
+//   upload (one H2D per launch).  ``col0`` is the node's base column in a gh matrix of row
 //   stride CH — 0/CH==C for single-tree builds; a FOREST build (K trees
 //   or K classes grown level-synchronously, reference
 //   GBMClassifier.scala:377-411 parallel futures) interleaves per-tree
 //   channel groups [g_t, h_t(, cnt_t)] and sets col0 = tree * C, so one
 //   launch histograms every active node of every tree.
 //   Flush converts back to f32 into out [n_nodes, F, B, C]; single-chunk
-//   nodes use plain stores, multi-chunk nodes integer staging atomics.
+//   nodes (stage_slot < 0) use plain stores, multi-chunk nodes integer
+//   atomics into their slot of the staging buffer.
 // ---------------------------------------------------------------------------
 
 template <int DC, int NC>
 __global__ void hist_build_kernel(
     float* __restrict__ out,            // [n_nodes, F, B, C]
-    long long* __restrict__ stage,      // [n_nodes, F, B, C] i64 (multi-chunk)
+    long long* __restrict__ stage,      // [n_multi, F, B, C] i64 (multi-chunk)
     const uint8_t* __restrict__ bins,   // [N, F]
     const float* __restrict__ gh,       // [N, CH]
     const int* __restrict__ row_idx,    // [M]
@@ -272,7 +263,7 @@ __global__ void hist_build_kernel(
   const int node = chk[0];
   const int start = chk[1];
   const int len = chk[2];
-  const int single = chk[3];
+  const int slot = chk[3];
   const int col0 = chk[4];
 
   const int lds_cells = FG * B * CELLS;
@@ -336,7 +327,7 @@ __global__ void hist_build_kernel(
   // into the i64 staging buffer — integer atomics are order-independent,
   // so histograms stay bitwise deterministic across runs (decode kernel
   // below converts once at the end).
-  if (single) {
+  if (slot < 0) {
     float* dst = out + (((int64_t)node * F + f0) * B) * C;
     for (int i = threadIdx.x; i < nf * B; i += blockDim.x) {
       const int f = i / B, b = i - f * B;
@@ -351,7 +342,7 @@ __global__ void hist_build_kernel(
             (float)(int)(unsigned)(cell[c] & 0xFFFFFFFFull) / scales[DC + c];
     }
   } else {
-    long long* sdst = stage + (((int64_t)node * F + f0) * B) * C;
+    long long* sdst = stage + (((int64_t)slot * F + f0) * B) * C;
     for (int i = threadIdx.x; i < nf * B; i += blockDim.x) {
       const int f = i / B, b = i - f * B;
       const unsigned long long* cell = lds64 + ((f * B) + b) * CELLS;
@@ -375,35 +366,47 @@ __global__ void hist_build_kernel(
 // decode the i64 staging sums of multi-chunk nodes into f32 out
 __global__ void hist_decode_kernel(float* __restrict__ out,
                                    const long long* __restrict__ stage,
-                                   const int* __restrict__ nodes,  // multi-chunk node ids (after scales)
-                                   const float* __restrict__ scales, int FBC,
-                                   int C) {
-  const int node = nodes[blockIdx.y];
-  const int64_t base = (int64_t)node * FBC;
+                                   const int* __restrict__ nodes,  // [n_multi] node of each slot
+                                   const float* __restrict__ scales,  // [C]
+                                   int64_t FBC, int C) {
+  const int64_t obase = (int64_t)nodes[blockIdx.y] * FBC;
+  const int64_t sbase = (int64_t)blockIdx.y * FBC;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < FBC;
        i += gridDim.x * (int64_t)blockDim.x) {
     const int c = (int)(i % C);
-    out[base + i] = (float)stage[base + i] / scales[c];
+    out[obase + i] = (float)stage[sbase + i] / scales[c];
   }
 }
 
-void hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
-                torch::Tensor row_idx, torch::Tensor node_offsets,
-                int64_t num_bins, int64_t d_dims, torch::Tensor max_abs,
-                bool identity_rows, torch::Tensor node_col0,
-                int64_t c_per_node) {
+void launch_hist_decode(float* out, const long long* stage, const int* nodes,
+                        const float* scales, int n_multi, int64_t FBC, int C,
+                        hipStream_t stream) {
+  const int dblocks = (int)std::min<int64_t>(ceil_div(FBC, 256), 1024);
+  hipLaunchKernelGGL(hist_decode_kernel, dim3(dblocks, n_multi), dim3(256), 0,
+                     stream, out, stage, nodes, scales, FBC, C);
+}
+
+// Returns the number of multi-chunk nodes.
+int64_t hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
+                   torch::Tensor row_idx, torch::Tensor node_offsets,
+                   int64_t num_bins, int64_t d_dims, torch::Tensor max_abs,
+                   bool identity_rows, torch::Tensor node_col0,
+                   int64_t c_per_node) {
   CHECK_GPU(out); CHECK_GPU(bins); CHECK_GPU(gh); CHECK_GPU(row_idx);
   CHECK_CONTIG(out); CHECK_CONTIG(bins); CHECK_CONTIG(gh); CHECK_CONTIG(row_idx);
   TORCH_CHECK(!node_offsets.is_cuda(), "node_offsets stays on host");
   TORCH_CHECK(!max_abs.is_cuda(), "max_abs stays on host");
+  TORCH_CHECK(!node_col0.is_cuda(), "node_col0 stays on host");
+  CHECK_CONTIG(node_offsets); CHECK_CONTIG(node_col0);
   const int F = (int)bins.size(1);
   const int B = (int)num_bins;
   const int CH = (int)gh.size(1);  // gh row stride
   // channels PER NODE: gh width for single-tree builds; explicit for
   // forest builds where gh interleaves per-tree channel groups
   const int C = c_per_node > 0 ? (int)c_per_node : CH;
+  const int n_nodes = (int)node_offsets.numel() - 1;
   const bool forest = node_col0.numel() > 0;
-  TORCH_CHECK(!forest || node_col0.numel() == node_offsets.numel() - 1,
+  TORCH_CHECK(!forest || node_col0.numel() == n_nodes,
               "node_col0 must have one entry per node");
   const int D = d_dims > 0 ? (int)d_dims : (C >= 3 ? C - 2 : C - 1);
   const int NN = C - D;
@@ -412,10 +415,17 @@ void hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
               "hist_build: channels must be D grads + 1-2 nonneg, got C=", C,
               " D=", D);
   TORCH_CHECK(max_abs.numel() == C, "max_abs must have C entries");
+  TORCH_CHECK(out.numel() == (int64_t)n_nodes * F * B * C,
+              "out must be [n_nodes, F, B, C]");
+  if (n_nodes == 0 || F == 0) return 0;
   const int CELLS = std::max(D, NN);
 
-  // feature-group size: 16 (32-KiB LDS at CELLS=1) or 32 (64-KiB, halves
-  // the random-row read amplification at deep levels); SEA_HIST_FG overrides
+  // feature-group size by CELLS, probe-measured
+  // (profiles/r01_hist_probe3): CELLS==1 -> FG=64 / 1024 threads / 128 KiB
+  // LDS (1 block/CU; 64-B row slices quarter the random-row fetch
+  // amplification); CELLS==2 -> FG=32 / 1024; CELLS>=3 (multiclass) ->
+  // FG=16 / 512 in ~99 KiB, which keeps the vectorized uint4 row loads.
+  // SEA_HIST_FG caps FG, SEA_HIST_LDS the LDS budget.
   static const int fg_env = []() {
     const char* e = getenv("SEA_HIST_FG");
     return e ? atoi(e) : 0;
@@ -424,19 +434,7 @@ void hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
     const char* e = getenv("SEA_HIST_LDS");
     return e ? atoi(e) : 163840;  // up to the full 160 KiB LDS per CU
   }();
-  // measured (profiles/r01_hist_probe3): FG=64 + 1024 threads + 128 KiB
-  // LDS (1 block/CU, 16 waves) runs 1.9x FG=16/256 — 64-B row slices
-  // quarter the random-row fetch amplification and the wider block keeps
-  // the LDS atomic pipe fed
-  // probe-measured optima (profiles/r01_hist_probe3): CELLS==1 ->
-  // FG=64 / 1024 threads / 128 KiB; CELLS==2 -> FG=32 / 1024 / 128 KiB;
-  // CELLS>=3 (wide multiclass) keeps the conservative 64-KiB config
-  // CELLS>=3 (multiclass): FG=16 fits in ~99 KiB with the B+1-free
-  // layout and keeps the vectorized uint4 row loads; the old 64-KiB cap
-  // forced FG=8 byte loads and DOUBLED the per-row gh re-reads (one per
-  // feature group)
-  const int budget = lds_budget;
-  int FG = std::max<int>(1, std::min<int>(F, budget / (B * CELLS * 8)));
+  int FG = std::max<int>(1, std::min<int>(F, lds_budget / (B * CELLS * 8)));
   if (CELLS == 1 && FG >= 64 && (F % 64) == 0) FG = 64;
   else if (CELLS <= 2 && FG >= 32 && (F % 32) == 0) FG = 32;
   else if (FG >= 16) FG = 16;
@@ -448,87 +446,36 @@ void hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
       (FG >= 64 || (CELLS == 2 && FG >= 32)) ? 1024
       : ((FG >= 32 || (CELLS >= 3 && FG >= 16)) ? 512 : 256);
   const int n_groups = (int)ceil_div(F, FG);
+  const size_t lds_bytes = (size_t)FG * B * CELLS * 8;
 
-  // ---- adaptive chunking: target ~resident-grid x OVERSUB blocks --------
-  const int n_nodes = (int)node_offsets.numel() - 1;
-  auto offs = node_offsets.accessor<int64_t, 1>();
-  int64_t total_rows = 0;
-  for (int nd = 0; nd < n_nodes; ++nd) total_rows += offs[nd + 1] - offs[nd];
-  const size_t lds_bytes_pre = (size_t)FG * B * CELLS * 8;
-  const int blocks_per_cu =
-      std::max<int>(1, (int)(163840 / std::max<size_t>(1, lds_bytes_pre)));
-  const int64_t resident = (int64_t)256 * blocks_per_cu;
-  // oversubscription: exactly-resident grids measured fastest at 1
-  // block/CU (probe3); modest oversub amortizes imbalance otherwise
-  static const double oversub_env = []() {
-    const char* e = getenv("SEA_HIST_OVERSUB");
-    return e ? atof(e) : 0.0;
-  }();
-  const double oversub =
-      oversub_env > 0 ? oversub_env : (blocks_per_cu == 1 ? 1.0 : 1.5);
-  const int64_t target_chunks = std::max<int64_t>(
-      1, (int64_t)(resident * oversub) / std::max(1, n_groups));
-  int64_t chunk_rows = std::max<int64_t>(
-      4096, ceil_div(total_rows, target_chunks));
-  // fixed-point headroom: per-chunk per-bin |sum| must stay < 2^30
-  const int64_t CHUNK_CAP = 1 << 20;
-  chunk_rows = std::min(chunk_rows, CHUNK_CAP);
+  HistPlan plan = plan_hist_chunks(
+      node_offsets.data_ptr<int64_t>(), n_nodes,
+      forest ? node_col0.data_ptr<int>() : nullptr,
+      identity_rows ? bins.size(0) : row_idx.numel(), CH - C + 1, lds_bytes,
+      n_groups, 2 * C);
 
-  // quantization scales: scale_c = 2^30 / (chunk_rows * max_abs_c)
+  // header: per-channel quantization scales
   auto max_abs_f = max_abs.to(torch::kFloat32).contiguous();
   auto ma = max_abs_f.accessor<float, 1>();
-  std::vector<int> chunk_v(2 * C);
-  float* scales_f = reinterpret_cast<float*>(chunk_v.data());
-  for (int c = 0; c < C; ++c) {
-    float m = ma[c];
-    if (!(m > 0.0f) || !std::isfinite(m)) m = 1.0f;
-    double s = (double)(1u << 30) / ((double)chunk_rows * (double)m);
-    // clamp so a single value cannot overflow int32 either
-    s = std::min(s, (double)(1u << 30) / (double)m);
-    scales_f[c] = (float)s;
-  }
-  const int* col0_p = forest ? node_col0.data_ptr<int>() : nullptr;
-  std::vector<int> multi_nodes;
-  for (int nd = 0; nd < n_nodes; ++nd) {
-    int64_t s = offs[nd], e = offs[nd + 1];
-    const int single = (e - s) <= chunk_rows ? 1 : 0;
-    if (!single) multi_nodes.push_back(nd);
-    if (e == s) {
-      // `out` is allocated uninitialized (flush/decode fully overwrite
-      // every chunked node) — a ZERO-ROW node emits no chunk, so its
-      // slice must be zeroed here (rank-local empty nodes are real in
-      // sharded fits: this node's rows may all live on other ranks)
-      out.slice(0, nd, nd + 1).zero_();
-    }
-    for (int64_t c = s; c < e; c += chunk_rows) {
-      chunk_v.push_back(nd);
-      chunk_v.push_back((int)c);
-      chunk_v.push_back((int)std::min<int64_t>(chunk_rows, e - c));
-      chunk_v.push_back(single);
-      chunk_v.push_back(col0_p ? col0_p[nd] : 0);
-    }
-  }
-  if ((int)chunk_v.size() == 2 * C) {
-    out.zero_();  // dispatch allocates `out` uninitialized
-    return;
-  }
-  const int n_chunks = (int)((chunk_v.size() - 2 * C) / 5);
-  auto chunks_b = h2d_async(chunk_v.data(), chunk_v.size() * 4, 0,
-                            bins.device());
-  auto chunks = chunks_b.view(torch::kInt32);
+  float* scales_f = reinterpret_cast<float*>(plan.table.data());
+  for (int c = 0; c < C; ++c)
+    scales_f[c] = (float)hist_fixed_scale(plan.chunk_rows, ma[c]);
+  auto chunks = h2d_async(plan.table.data(), plan.table.size() * 4,
+                          kSlotHistChunks, bins.device())
+                    .view(torch::kInt32);
 
   // i64 integer staging for multi-chunk nodes (order-independent flush =>
   // bitwise-deterministic histograms)
+  const int n_multi = (int)plan.multi_nodes.size();
   torch::Tensor stage;
   long long* stage_ptr = nullptr;
-  if (!multi_nodes.empty()) {
-    stage = torch::zeros({(int64_t)n_nodes, (int64_t)F, (int64_t)B, (int64_t)C},
+  if (n_multi) {
+    stage = torch::zeros({(int64_t)n_multi, (int64_t)F, (int64_t)B, (int64_t)C},
                          out.options().dtype(torch::kInt64));
     stage_ptr = reinterpret_cast<long long*>(stage.data_ptr<int64_t>());
   }
 
   auto stream = at::hip::getCurrentHIPStream();
-  const size_t lds_bytes = lds_bytes_pre;
 #define HB_LAUNCH(DD, NNN)                                                   \
   do {                                                                       \
     if (lds_bytes > 65536)                                                   \
@@ -536,8 +483,8 @@ void hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
           reinterpret_cast<const void*>(&hist_build_kernel<DD, NNN>),        \
           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);       \
     hipLaunchKernelGGL((hist_build_kernel<DD, NNN>),                         \
-                       dim3(n_chunks, n_groups), dim3(threads), lds_bytes,   \
-                       stream, out.data_ptr<float>(), stage_ptr,             \
+                       dim3(plan.n_chunks, n_groups), dim3(threads),         \
+                       lds_bytes, stream, out.data_ptr<float>(), stage_ptr,  \
                        bins.data_ptr<uint8_t>(),                             \
                        gh.data_ptr<float>(), row_idx.data_ptr<int>(),        \
                        chunks.data_ptr<int>(), F, B, FG, CH,                 \
@@ -561,19 +508,15 @@ void hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
     default: TORCH_CHECK(false, "hist_build: unsupported D/NN ", D, "/", NN);
   }
 #undef HB_LAUNCH
-  if (!multi_nodes.empty()) {
-    auto nodes_b = h2d_async(multi_nodes.data(), multi_nodes.size() * 4, 1,
-                             bins.device());
-    auto nodes_t = nodes_b.view(torch::kInt32);
-    const int FBC = F * B * C;
-    const int dblocks = (int)std::min<int64_t>(ceil_div(FBC, 256), 1024);
-    hipLaunchKernelGGL(hist_decode_kernel,
-                       dim3(dblocks, (int)multi_nodes.size()), dim3(256), 0,
-                       stream, out.data_ptr<float>(), stage_ptr,
-                       nodes_t.data_ptr<int>(),
+  if (n_multi) {
+    auto nodes = h2d_async(plan.multi_nodes.data(), (size_t)n_multi * 4,
+                           kSlotHistNodes, bins.device());
+    launch_hist_decode(out.data_ptr<float>(), stage_ptr,
+                       (const int*)nodes.data_ptr(),
                        reinterpret_cast<const float*>(chunks.data_ptr<int>()),
-                       FBC, C);
+                       n_multi, (int64_t)F * B * C, C, stream);
   }
+  return n_multi;
 }
 
 // ---------------------------------------------------------------------------
@@ -702,11 +645,12 @@ void partition_rows(torch::Tensor new_rows, torch::Tensor left_counts,
   auto stream = at::hip::getCurrentHIPStream();
   static const bool part_dbg = getenv("SEA_PART_DEBUG") != nullptr;
   auto tp0 = std::chrono::steady_clock::now();
-  auto cursors_b = h2d_async(cur_v.data(), cur_v.size() * 4, 2, bins.device());
+  auto cursors_b = h2d_async(cur_v.data(), cur_v.size() * 4,
+                             kSlotPartCursors, bins.device());
   auto cursors = cursors_b.view(torch::kInt32);
   auto tp1 = std::chrono::steady_clock::now();
   if (!chunk_v.empty()) {
-    auto chunks_b = h2d_async(chunk_v.data(), chunk_v.size() * 4, 3,
+    auto chunks_b = h2d_async(chunk_v.data(), chunk_v.size() * 4, kSlotPartChunks,
                               bins.device());
     auto chunks = chunks_b.view(torch::kInt32);
     auto tp2 = std::chrono::steady_clock::now();
@@ -740,7 +684,8 @@ void partition_rows(torch::Tensor new_rows, torch::Tensor left_counts,
   // (found via SEA_PART_DEBUG bracketing); pinned async staging fixes it
   std::vector<int> seg_v(n_nodes);
   for (int nd = 0; nd < n_nodes; ++nd) seg_v[nd] = (int)offs[nd];
-  auto seg_b = h2d_async(seg_v.data(), seg_v.size() * 4, 4, bins.device());
+  auto seg_b = h2d_async(seg_v.data(), seg_v.size() * 4, kSlotPartSegStart,
+                         bins.device());
   auto seg_start = seg_b.view(torch::kInt32);
   left_counts.copy_(lcur - seg_start);
 }
@@ -1014,7 +959,8 @@ void gather_ranges(torch::Tensor out, torch::Tensor src,
     seg_v[n_segs + 1 + i] = st[i];
   }
   TORCH_CHECK(seg_v[n_segs] == total, "gather_ranges: lens sum != out size");
-  auto seg_b = h2d_async(seg_v.data(), seg_v.size() * 8, 5, src.device());
+  auto seg_b = h2d_async(seg_v.data(), seg_v.size() * 8, kSlotGatherSegs,
+                         src.device());
   auto stream = at::hip::getCurrentHIPStream();
   const int blocks =
       (int)std::min<long long>(8192, ceil_div(total, (long long)1024));
@@ -1040,16 +986,17 @@ void leaf_scatter(torch::Tensor tp, torch::Tensor row_idx,
   }
   const long long total = seg_v[n_segs];
   if (total == 0) return;
-  auto seg_b = h2d_async(seg_v.data(), seg_v.size() * 8, 5, tp.device());
+  auto seg_b = h2d_async(seg_v.data(), seg_v.size() * 8, kSlotLeafSegs,
+                         tp.device());
   std::vector<int> tv(n_segs);
   std::vector<float> vv(n_segs);
   auto ta = tree.accessor<int64_t, 1>();
   auto va = val.accessor<float, 1>();
   for (int i = 0; i < n_segs; ++i) { tv[i] = (int)ta[i]; vv[i] = va[i]; }
-  auto tree_b = h2d_async(tv.data(), tv.size() * 4, 6, tp.device());
+  auto tree_b = h2d_async(tv.data(), tv.size() * 4, kSlotLeafTree, tp.device());
   std::vector<char> vb(n_segs * 4);
   std::memcpy(vb.data(), vv.data(), n_segs * 4);
-  auto val_b = h2d_async(vb.data(), vb.size(), 7, tp.device());
+  auto val_b = h2d_async(vb.data(), vb.size(), kSlotLeafVal, tp.device());
   auto stream = at::hip::getCurrentHIPStream();
   const int blocks =
       (int)std::min<long long>(8192, ceil_div(total, (long long)1024));
@@ -1555,15 +1502,6 @@ void line_search_eval(torch::Tensor payload, torch::Tensor label,
 //   a per-node cell — no [n,F,B,C] cumsum/gain tensors ever touch HBM.
 // ---------------------------------------------------------------------------
 
-__device__ inline unsigned f32_sortable(float f) {
-  unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float sortable_f32(unsigned s) {
-  unsigned u = (s & 0x80000000u) ? (s & 0x7FFFFFFFu) : ~s;
-  return __uint_as_float(u);
-}
-
 template <int C>
 __global__ void split_argmax_kernel(
     unsigned long long* __restrict__ best,  // [n_nodes] pre-zeroed
@@ -1697,13 +1635,6 @@ __global__ void split_decode_kernel(
   if (threadIdx.x < C) left_stats[node * C + threadIdx.x] = acc[threadIdx.x];
 }
 
-// csrc/wide_class.hip: one wave per (node, feature), channel loop in LDS
-void split_argmax_wide(torch::Tensor gain, torch::Tensor feat,
-                       torch::Tensor bin, torch::Tensor left_stats,
-                       torch::Tensor hist, int D, double lam,
-                       double min_child_weight, double min_instances,
-                       double min_info_gain);
-
 void split_argmax(torch::Tensor gain, torch::Tensor feat, torch::Tensor bin,
                   torch::Tensor left_stats, torch::Tensor hist, int64_t d_dims,
                   double lam, double min_child_weight, double min_instances,
@@ -1753,20 +1684,28 @@ void split_argmax(torch::Tensor gain, torch::Tensor feat, torch::Tensor bin,
 #undef SA_LAUNCH
 }
 
-// csrc/linear.hip
-void logreg_loss_grad(torch::Tensor payload, torch::Tensor x, torch::Tensor y,
-                      torch::Tensor w, torch::Tensor wmat, bool has_bias);
-bool logreg_fused_supported(int64_t F, int64_t K);
-
-// csrc/wide_class.hip
-int64_t hist_build_class(torch::Tensor out, torch::Tensor bins,
-                         torch::Tensor bins_t, torch::Tensor label,
-                         torch::Tensor weight, torch::Tensor row_idx,
-                         torch::Tensor node_offsets, torch::Tensor node_col0,
-                         int64_t num_bins, int64_t num_classes, int64_t nn,
-                         double w_max, bool identity_rows);
+// csrc/hist_plan.h on host tensors, for tests: touches no device
+std::tuple<int64_t, torch::Tensor, torch::Tensor> hist_plan_debug(
+    torch::Tensor node_offsets, torch::Tensor node_col0, int64_t row_bound,
+    int64_t col_bound, int64_t lds_bytes, int64_t n_groups) {
+  auto offs = node_offsets.to(torch::kInt64).contiguous();
+  auto col0 = node_col0.to(torch::kInt32).contiguous();
+  const int n_nodes = (int)offs.numel() - 1;
+  TORCH_CHECK(col0.numel() == 0 || col0.numel() == n_nodes,
+              "node_col0 must be empty or have one entry per node");
+  HistPlan plan = plan_hist_chunks(
+      offs.data_ptr<int64_t>(), n_nodes,
+      col0.numel() ? col0.data_ptr<int>() : nullptr, row_bound,
+      (int)col_bound, (size_t)lds_bytes, (int)n_groups, 0);
+  auto i32 = torch::TensorOptions().dtype(torch::kInt32);
+  auto chunks = torch::tensor(plan.table, i32).view({plan.n_chunks, 5});
+  auto multi = torch::tensor(plan.multi_nodes, i32);
+  return {plan.chunk_rows, chunks, multi};
+}
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("_hist_plan", &hist_plan_debug,
+        "host-side chunk plan of the histogram kernels (no device)");
   m.def("logreg_loss_grad", &logreg_loss_grad,
         "single-pass fused logistic loss+gradient");
   m.def("logreg_fused_supported", &logreg_fused_supported);

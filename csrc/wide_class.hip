@@ -21,32 +21,22 @@
 //     2^floor(log2(2^30 / (chunk_rows * w_max))),
 // so weights that are integer multiples of 1/scale (unit weights, Poisson
 // bootstrap counts) histogram EXACTLY, and decoding is an exact multiply.
-// Chunking, CHUNK_CAP, single-chunk plain-store flush and the i64 staging
-// path for multi-chunk nodes (bitwise deterministic) follow hist_build.
+// Chunking, the single-chunk plain-store flush and the i64 staging slots of
+// multi-chunk nodes (bitwise deterministic) come from csrc/hist_plan.h, the
+// same plan hist_build uses; the staging decode is ops.hip's.
 
-#include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#define WC_CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be on GPU")
-#define WC_CHECK_CONTIG(x) \
-  TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
-
-// csrc/ops.hip: pinned ping-pong staging upload (see the postmortem there)
-torch::Tensor sea_h2d_async(const void* src, size_t bytes, int slot,
-                            const torch::Device& dev);
-
-static inline int64_t wc_ceil_div(int64_t a, int64_t b) {
-  return (a + b - 1) / b;
-}
+#include "common.h"
+#include "hist_plan.h"
 
 // chunk table: int32 [2 + n_chunks * 5]; words 0/1 are the f32 scale and
-// its exact reciprocal, then per chunk (node, start, len, stage_slot, col0)
-// with stage_slot < 0 for single-chunk nodes (plain-store flush).
+// its exact reciprocal, then the plan's records (node, start, len,
+// stage_slot, col0) with stage_slot < 0 for single-chunk nodes.
 __global__ __launch_bounds__(1024) void hist_class_kernel(
     float* __restrict__ out,              // [n_nodes, F, B, K + NN]
     long long* __restrict__ stage,        // [n_multi, F, B, K + NN] i64
@@ -57,7 +47,7 @@ __global__ __launch_bounds__(1024) void hist_class_kernel(
     const int* __restrict__ row_idx,      // [M]
     const int* __restrict__ chunks, int64_t N, int F, int B, int K, int NN,
     int FG, int T, int identity_rows) {
-  extern __shared__ unsigned long long wc_lds[];  // FG * B * K cells
+  extern __shared__ unsigned long long cls_lds[];  // FG * B * K cells
   const float scale = __int_as_float(chunks[0]);
   const float inv_scale = __int_as_float(chunks[1]);
   const int* chk = chunks + 2 + blockIdx.x * 5;
@@ -71,7 +61,7 @@ __global__ __launch_bounds__(1024) void hist_class_kernel(
   const int C = K + NN;
 
   const int lds_cells = nf * B * K;
-  for (int i = threadIdx.x; i < lds_cells; i += blockDim.x) wc_lds[i] = 0ull;
+  for (int i = threadIdx.x; i < lds_cells; i += blockDim.x) cls_lds[i] = 0ull;
   __syncthreads();
 
   for (int i = threadIdx.x; i < len; i += blockDim.x) {
@@ -85,13 +75,13 @@ __global__ __launch_bounds__(1024) void hist_class_kernel(
       const uint8_t* bc = bins_t + (int64_t)f0 * N + r;
       for (int f = 0; f < nf; ++f) {
         const int b = bc[(int64_t)f * N];
-        if (b < B) atomicAdd(wc_lds + ((f * B) + b) * K + k, addend);
+        if (b < B) atomicAdd(cls_lds + ((f * B) + b) * K + k, addend);
       }
     } else {
       const uint8_t* br = bins + (int64_t)r * F + f0;
       for (int f = 0; f < nf; ++f) {
         const int b = br[f];
-        if (b < B) atomicAdd(wc_lds + ((f * B) + b) * K + k, addend);
+        if (b < B) atomicAdd(cls_lds + ((f * B) + b) * K + k, addend);
       }
     }
   }
@@ -103,7 +93,7 @@ __global__ __launch_bounds__(1024) void hist_class_kernel(
   // (K = 32 would otherwise serialise 32-way).  hess and count are the
   // INTEGER sums over the classes, decoded once.
   for (int fb = threadIdx.x; fb < nf * B; fb += blockDim.x) {
-    const unsigned long long* cell = wc_lds + (int64_t)fb * K;
+    const unsigned long long* cell = cls_lds + (int64_t)fb * K;
     const int64_t o_off = (((int64_t)f0 * B) + fb) * C;
     long long hs = 0, cs = 0;
     int k = fb % K;
@@ -136,22 +126,6 @@ __global__ __launch_bounds__(1024) void hist_class_kernel(
   }
 }
 
-// decode the i64 staging sums of multi-chunk nodes into f32 out
-__global__ void hist_class_decode_kernel(
-    float* __restrict__ out, const long long* __restrict__ stage,
-    const int* __restrict__ nodes,  // [n_multi] node id of each stage slot
-    float inv_scale, int64_t FBC, int C, int K) {
-  const int slot = blockIdx.y;
-  const int64_t obase = (int64_t)nodes[slot] * FBC;
-  const int64_t sbase = (int64_t)slot * FBC;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < FBC;
-       i += gridDim.x * (int64_t)blockDim.x) {
-    const int c = (int)(i % C);
-    const float s = c > K ? 1.0f : inv_scale;  // channel K + 1 is a count
-    out[obase + i] = (float)stage[sbase + i] * s;
-  }
-}
-
 // Returns the number of multi-chunk nodes (callers/tests can tell which
 // flush path a launch took).
 int64_t hist_build_class(torch::Tensor out, torch::Tensor bins,
@@ -160,10 +134,10 @@ int64_t hist_build_class(torch::Tensor out, torch::Tensor bins,
                          torch::Tensor node_offsets, torch::Tensor node_col0,
                          int64_t num_bins, int64_t num_classes, int64_t nn,
                          double w_max, bool identity_rows) {
-  WC_CHECK_GPU(out); WC_CHECK_GPU(bins); WC_CHECK_GPU(label);
-  WC_CHECK_GPU(weight); WC_CHECK_GPU(row_idx);
-  WC_CHECK_CONTIG(out); WC_CHECK_CONTIG(bins); WC_CHECK_CONTIG(label);
-  WC_CHECK_CONTIG(weight); WC_CHECK_CONTIG(row_idx);
+  CHECK_GPU(out); CHECK_GPU(bins); CHECK_GPU(label);
+  CHECK_GPU(weight); CHECK_GPU(row_idx);
+  CHECK_CONTIG(out); CHECK_CONTIG(bins); CHECK_CONTIG(label);
+  CHECK_CONTIG(weight); CHECK_CONTIG(row_idx);
   TORCH_CHECK(!node_offsets.is_cuda(), "node_offsets stays on host");
   TORCH_CHECK(!node_col0.is_cuda(), "node_col0 stays on host");
   TORCH_CHECK(bins.scalar_type() == torch::kUInt8 &&
@@ -194,7 +168,7 @@ int64_t hist_build_class(torch::Tensor out, torch::Tensor bins,
               "out must be [n_nodes, F, B, K + NN]");
   const bool transposed = bins_t.numel() > 0;
   if (transposed) {
-    WC_CHECK_GPU(bins_t); WC_CHECK_CONTIG(bins_t);
+    CHECK_GPU(bins_t); CHECK_CONTIG(bins_t);
     TORCH_CHECK(bins_t.size(0) == F && bins_t.size(1) == N,
                 "bins_t must be the [F, N] transpose of bins");
   }
@@ -206,82 +180,33 @@ int64_t hist_build_class(torch::Tensor out, torch::Tensor bins,
   const int budget = 163840;
   int FG = std::max(1, std::min(F, budget / (B * K * 8)));
   FG = std::min(FG, 16);
-  const int n_groups = (int)wc_ceil_div(F, FG);
-  FG = (int)wc_ceil_div(F, n_groups);
+  const int n_groups = (int)ceil_div(F, FG);
+  FG = (int)ceil_div(F, n_groups);
   const size_t lds_bytes = (size_t)FG * B * K * 8;
   const int blocks_per_cu = std::max<int>(1, (int)(budget / lds_bytes));
   const int threads = blocks_per_cu == 1 ? 1024 : (blocks_per_cu == 2 ? 512 : 256);
 
-  // ---- adaptive chunking (same policy as hist_build) ----------------------
-  auto offs = node_offsets.accessor<int64_t, 1>();
-  auto col0 = node_col0.accessor<int, 1>();
-  const int64_t M = row_idx.numel();
-  int64_t total_rows = 0;
-  for (int nd = 0; nd < n_nodes; ++nd) {
-    const int64_t s = offs[nd], e = offs[nd + 1];
-    TORCH_CHECK(s >= 0 && e >= s && (identity_rows ? e <= N : e <= M),
-                "hist_build_class: node_offsets out of range");
-    TORCH_CHECK(col0[nd] >= 0 && col0[nd] < T,
-                "hist_build_class: node_col0 out of range");
-    total_rows += e - s;
-  }
-  const int64_t resident = (int64_t)256 * blocks_per_cu;
-  static const double oversub_env = []() {
-    const char* e = getenv("SEA_HIST_OVERSUB");
-    return e ? atof(e) : 0.0;
-  }();
-  const double oversub =
-      oversub_env > 0 ? oversub_env : (blocks_per_cu == 1 ? 1.0 : 1.5);
-  const int64_t target_chunks = std::max<int64_t>(
-      1, (int64_t)(resident * oversub) / std::max(1, n_groups));
-  int64_t chunk_rows =
-      std::max<int64_t>(4096, wc_ceil_div(total_rows, target_chunks));
-  const int64_t CHUNK_CAP = 1 << 20;  // count field and 2^30 weight headroom
-  chunk_rows = std::min(chunk_rows, CHUNK_CAP);
+  CHECK_CONTIG(node_offsets); CHECK_CONTIG(node_col0);
+  HistPlan plan = plan_hist_chunks(
+      node_offsets.data_ptr<int64_t>(), n_nodes, node_col0.data_ptr<int>(),
+      identity_rows ? N : row_idx.numel(), T, lds_bytes, n_groups, 2);
 
-  // scale = 2^30 / (chunk_rows * w_max) rounded DOWN to a power of two,
-  // clamped so a single value cannot overflow
-  double wm = w_max;
-  if (!(wm > 0.0) || !std::isfinite(wm)) wm = 1.0;
-  double s_raw = (double)(1u << 30) / ((double)chunk_rows * wm);
-  s_raw = std::min(s_raw, (double)(1u << 30) / wm);
-  const float scale = (float)std::exp2(std::floor(std::log2(s_raw)));
-  const float inv_scale = 1.0f / scale;  // exact: power of two
+  // header: the fixed-point scale rounded DOWN to a power of two, and its
+  // exact reciprocal
+  const float scale = (float)std::exp2(
+      std::floor(std::log2(hist_fixed_scale(plan.chunk_rows, w_max))));
+  const float inv_scale = 1.0f / scale;
+  std::memcpy(&plan.table[0], &scale, 4);
+  std::memcpy(&plan.table[1], &inv_scale, 4);
+  auto chunks = h2d_async(plan.table.data(), plan.table.size() * 4,
+                          kSlotClassChunks, bins.device())
+                    .view(torch::kInt32);
 
-  std::vector<int> chunk_v(2);
-  std::memcpy(&chunk_v[0], &scale, 4);
-  std::memcpy(&chunk_v[1], &inv_scale, 4);
-  std::vector<int> multi_nodes;
-  for (int nd = 0; nd < n_nodes; ++nd) {
-    const int64_t s = offs[nd], e = offs[nd + 1];
-    int slot = -1;
-    if (e - s > chunk_rows) {
-      slot = (int)multi_nodes.size();
-      multi_nodes.push_back(nd);
-    }
-    // a zero-row node still gets ONE (empty) chunk: its blocks flush the
-    // zeroed LDS, so `out` needs no per-node zero fill
-    int64_t c = s;
-    do {
-      chunk_v.push_back(nd);
-      chunk_v.push_back((int)c);
-      chunk_v.push_back((int)std::min<int64_t>(chunk_rows, e - c));
-      chunk_v.push_back(slot);
-      chunk_v.push_back(col0[nd]);
-      c += chunk_rows;
-    } while (c < e);
-  }
-  const int n_chunks = (int)((chunk_v.size() - 2) / 5);
-  // staging slots 8/9 belong to this call site alone within a level
-  auto chunks_b =
-      sea_h2d_async(chunk_v.data(), chunk_v.size() * 4, 8, bins.device());
-  auto chunks = chunks_b.view(torch::kInt32);
-
+  const int n_multi = (int)plan.multi_nodes.size();
   torch::Tensor stage;
   long long* stage_ptr = nullptr;
-  if (!multi_nodes.empty()) {
-    stage = torch::zeros({(int64_t)multi_nodes.size(), (int64_t)F, (int64_t)B,
-                          (int64_t)C},
+  if (n_multi) {
+    stage = torch::zeros({(int64_t)n_multi, (int64_t)F, (int64_t)B, (int64_t)C},
                          out.options().dtype(torch::kInt64));
     stage_ptr = reinterpret_cast<long long*>(stage.data_ptr<int64_t>());
   }
@@ -292,24 +217,28 @@ int64_t hist_build_class(torch::Tensor out, torch::Tensor bins,
         reinterpret_cast<const void*>(&hist_class_kernel),
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   hipLaunchKernelGGL(
-      hist_class_kernel, dim3(n_chunks, n_groups), dim3(threads), lds_bytes,
+      hist_class_kernel, dim3(plan.n_chunks, n_groups), dim3(threads), lds_bytes,
       stream, out.data_ptr<float>(), stage_ptr, bins.data_ptr<uint8_t>(),
       transposed ? bins_t.data_ptr<uint8_t>() : (const uint8_t*)nullptr,
       label.data_ptr<uint8_t>(), weight.data_ptr<float>(),
       row_idx.data_ptr<int>(), chunks.data_ptr<int>(), N, F, B, K, NN, FG, T,
       identity_rows ? 1 : 0);
-  if (!multi_nodes.empty()) {
-    auto nodes_b = sea_h2d_async(multi_nodes.data(), multi_nodes.size() * 4, 9,
-                                 bins.device());
-    auto nodes_t = nodes_b.view(torch::kInt32);
-    const int64_t FBC = (int64_t)F * B * C;
-    const int dblocks = (int)std::min<int64_t>(wc_ceil_div(FBC, 256), 1024);
-    hipLaunchKernelGGL(hist_class_decode_kernel,
-                       dim3(dblocks, (int)multi_nodes.size()), dim3(256), 0,
-                       stream, out.data_ptr<float>(), stage_ptr,
-                       nodes_t.data_ptr<int>(), inv_scale, FBC, C, K);
+  if (n_multi) {
+    // one upload: node of each staging slot, then the decode divisors (the
+    // scale for the K class channels and hess, 1 for the count channel)
+    std::vector<int> dec(plan.multi_nodes);
+    dec.resize(n_multi + C);
+    float* div = reinterpret_cast<float*>(dec.data() + n_multi);
+    for (int c = 0; c < C; ++c) div[c] = c > K ? 1.0f : scale;
+    auto dec_d = h2d_async(dec.data(), dec.size() * 4, kSlotClassNodes,
+                           bins.device())
+                     .view(torch::kInt32);
+    launch_hist_decode(
+        out.data_ptr<float>(), stage_ptr, dec_d.data_ptr<int>(),
+        reinterpret_cast<const float*>(dec_d.data_ptr<int>() + n_multi),
+        n_multi, (int64_t)F * B * C, C, stream);
   }
-  return (int64_t)multi_nodes.size();
+  return n_multi;
 }
 
 // ---------------------------------------------------------------------------
@@ -323,21 +252,12 @@ int64_t hist_build_class(torch::Tensor out, torch::Tensor bins,
 //   same validity tests, same packed atomicMax tie rule.
 // ---------------------------------------------------------------------------
 
-__device__ inline unsigned wc_f32_sortable(float f) {
-  unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float wc_sortable_f32(unsigned s) {
-  unsigned u = (s & 0x80000000u) ? (s & 0x7FFFFFFFu) : ~s;
-  return __uint_as_float(u);
-}
-
 __global__ __launch_bounds__(64) void split_argmax_wide_kernel(
     unsigned long long* __restrict__ best,  // [n_nodes] pre-zeroed
     const float* __restrict__ hist,         // [n_nodes, F, B, C]
     int F, int B, int C, int D, float lam, float min_child_weight,
     float min_instances) {
-  extern __shared__ float wc_sl[];  // [C][Bp] channel-major
+  extern __shared__ float split_lds[];  // [C][Bp] channel-major
   const int node = blockIdx.x;
   const int f = blockIdx.y;
   const int lane = threadIdx.x;
@@ -348,7 +268,7 @@ __global__ __launch_bounds__(64) void split_argmax_wide_kernel(
 
   for (int j = lane; j < B * C; j += 64) {
     const int b = j / C, c = j - b * C;
-    wc_sl[c * Bp + b] = h[j];
+    split_lds[c * Bp + b] = h[j];
   }
   __syncthreads();
 
@@ -359,7 +279,7 @@ __global__ __launch_bounds__(64) void split_argmax_wide_kernel(
   const int b0 = lane * BPL;
 
   for (int c = 0; c < C; ++c) {
-    const float* row = wc_sl + c * Bp;
+    const float* row = split_lds + c * Bp;
     float v[4];
     float tot = 0.0f;
 #pragma unroll
@@ -406,7 +326,7 @@ __global__ __launch_bounds__(64) void split_argmax_wide_kernel(
           cl[i] >= min_instances && cr >= min_instances) {
         const float gain =
             gl[i] / (hl[i] + lam) + gr[i] / (hr + lam) - parent_score;
-        const unsigned sg = wc_f32_sortable(gain);
+        const unsigned sg = f32_sortable(gain);
         if (sg > best_s) { best_s = sg; best_b = b; }
       }
     }
@@ -432,7 +352,7 @@ __global__ __launch_bounds__(64) void split_decode_wide_kernel(
   const int node = blockIdx.x;
   const int c = threadIdx.x;
   const unsigned long long p = best[node];
-  const float g = wc_sortable_f32((unsigned)(p >> 32));
+  const float g = sortable_f32((unsigned)(p >> 32));
   if (p == 0ull || !(g >= min_info_gain)) {
     if (c == 0) {
       gain[node] = -INFINITY;

@@ -97,7 +97,6 @@ def hist_build(bins, gh, row_idx, node_offsets, num_bins, d_dims=-1, max_abs=Non
         m = _require_hip("hist_build")
         if m is not None:
             n_nodes = node_offsets.numel() - 1
-            F = bins.shape[1]
             C = gh.shape[1]
             if max_abs is None:
                 max_abs = gh.abs().amax(dim=0).cpu()
@@ -136,30 +135,33 @@ def hist_build(bins, gh, row_idx, node_offsets, num_bins, d_dims=-1, max_abs=Non
                     if ci == len(spans) - 1:
                         parts.append(part[..., w:])  # tail once
                 return torch.cat(parts, dim=-1)
-            # every (node, f, b) cell is fully written by either the
-            # single-chunk flush or the multi-chunk decode — no zero fill
-            out = torch.empty(
-                n_nodes, F, num_bins, C, dtype=torch.float32, device=bins.device
+            return _hist_build_launch(
+                m, bins, gh, row_idx, node_offsets, _EMPTY_I32, num_bins, C,
+                max_abs, d_dims, identity_rows,
             )
-            m.hist_build(
-                out,
-                bins,
-                gh.contiguous(),
-                row_idx.to(torch.int32),
-                node_offsets.to(torch.int64).cpu(),
-                int(num_bins),
-                int(d_dims),
-                max_abs.to(torch.float32),
-                bool(identity_rows),
-                _EMPTY_I32,
-                0,
-            )
-            return out
     return reference.hist_build(bins, gh, row_idx, node_offsets, num_bins)
 
 
 _EMPTY_I32 = torch.empty(0, dtype=torch.int32)
 _EMPTY_U8 = torch.empty(0, dtype=torch.uint8)
+
+
+def _hist_build_launch(m, bins, gh, row_idx, node_offsets, node_col0,
+                       num_bins, c_per_node, max_abs, d_dims, identity_rows):
+    """Allocate ``out`` and run the native hist_build.  Every node's slice
+    is fully written by the kernel's flush or the staging decode (zero-row
+    nodes included), so ``out`` needs no zero fill."""
+    out = torch.empty(
+        node_offsets.numel() - 1, bins.shape[1], num_bins, c_per_node,
+        dtype=torch.float32, device=bins.device,
+    )
+    m.hist_build(
+        out, bins, gh.contiguous(), row_idx.to(torch.int32),
+        node_offsets.to(torch.int64).cpu().contiguous(), int(num_bins),
+        int(d_dims), max_abs.to(torch.float32), bool(identity_rows),
+        node_col0, int(c_per_node),
+    )
+    return out
 
 
 def hist_build_forest(bins, gh, row_idx, node_offsets, node_col0, num_bins,
@@ -175,22 +177,11 @@ def hist_build_forest(bins, gh, row_idx, node_offsets, node_col0, num_bins,
     if bins.is_cuda:
         m = _require_hip("hist_build")
         if m is not None:
-            n_nodes = node_offsets.numel() - 1
-            F = bins.shape[1]
-            out = torch.empty(
-                n_nodes, F, num_bins, c_per_node,
-                dtype=torch.float32, device=bins.device,
+            return _hist_build_launch(
+                m, bins, gh, row_idx, node_offsets,
+                node_col0.to(torch.int32).cpu().contiguous(), num_bins,
+                c_per_node, max_abs, d_dims, False,
             )
-            m.hist_build(
-                out, bins, gh.contiguous(), row_idx.to(torch.int32),
-                node_offsets.to(torch.int64).cpu(), int(num_bins),
-                int(d_dims),
-                max_abs.to(torch.float32),
-                False,
-                node_col0.to(torch.int32).cpu().contiguous(),
-                int(c_per_node),
-            )
-            return out
     return reference.hist_build_forest(
         bins, gh, row_idx, node_offsets, node_col0, num_bins, c_per_node
     )
@@ -234,7 +225,7 @@ def hist_build_class(bins, label, weight, row_idx, node_offsets, node_col0,
             n_multi = m.hist_build_class(
                 out, bins, bt, label, weight.contiguous(),
                 row_idx.to(torch.int32),
-                node_offsets.to(torch.int64).cpu(),
+                node_offsets.to(torch.int64).cpu().contiguous(),
                 node_col0.to(torch.int32).cpu().contiguous(),
                 int(num_bins), int(num_classes), int(nn), float(w_max),
                 bool(identity_rows),

@@ -62,10 +62,36 @@ def test_hist_build_matches_reference(hip, ref):
         [torch.randn(n, d, generator=g), torch.rand(n, 2, generator=g)], dim=1
     ).to(DEV)
     rows = torch.randperm(n, generator=g)[: n - 100].to(torch.int32).to(DEV)
-    offs = torch.tensor([0, 9000, 9000, n - 100])
+    # one launch with a single-chunk node, a multi-chunk node, an empty
+    # node and a second multi-chunk node (staging slot != node id)
+    offs = torch.tensor([0, 2000, 11000, 11000, n - 100])
     got = hip.hist_build(bins, gh, rows, offs, b, d)
     want = ref.hist_build(bins.cpu(), gh.cpu(), rows.cpu(), offs, b)
     assert torch.allclose(got.cpu(), want, atol=2e-2, rtol=1e-4)
+    assert torch.equal(got[2].cpu(), torch.zeros(f, b, d + 2))
+
+    import spark_ensemble_amd._hip_ops as m
+
+    out = torch.empty_like(got)
+    n_multi = m.hist_build(
+        out, bins, gh, rows, offs, b, d, gh.abs().amax(dim=0).cpu(), False,
+        torch.empty(0, dtype=torch.int32), 0,
+    )
+    assert n_multi == 2
+    assert torch.equal(out, got)
+
+
+def test_hist_build_all_nodes_empty(hip):
+    g = torch.Generator().manual_seed(2)
+    n, f, b, d = 3000, 40, 32, 2
+    bins = torch.randint(0, b, (n, f), generator=g, dtype=torch.uint8).to(DEV)
+    gh = torch.cat(
+        [torch.randn(n, d, generator=g), torch.rand(n, 2, generator=g)], dim=1
+    ).to(DEV)
+    rows = torch.empty(0, dtype=torch.int32, device=DEV)
+    got = hip.hist_build(bins, gh, rows, torch.tensor([0, 0, 0]), b, d)
+    assert got.shape == (2, f, b, d + 2)
+    assert torch.equal(got.cpu(), torch.zeros(2, f, b, d + 2))
 
 
 def test_hist_build_256bins_multiclass(hip, ref):

@@ -3,13 +3,14 @@
 Drives hipcc DIRECTLY (no hipify, no CUDA-compat pass): csrc/ops.hip is
 native HIP/CDNA4 code.  The resulting spark_ensemble_amd/_hip_ops.so lives
 in-tree so it travels to GPU boxes with the repo snapshot (it is
-git-ignored; gpurun ships it).
+git-ignored).
 
 Usage:  python tools/build_ext.py   (or via setup.py / __graft_entry__.build)
 """
 
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -25,6 +26,14 @@ OUT = os.path.join(REPO, "spark_ensemble_amd", "_hip_ops.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 
+def is_stale(out: str, deps: list) -> bool:
+    """True when ``out`` is missing or not newer than every file in ``deps``
+    (the .hip sources AND the headers they include)."""
+    if not os.path.exists(out):
+        return True
+    return os.path.getmtime(out) <= max(os.path.getmtime(d) for d in deps)
+
+
 def build(verbose: bool = True) -> str:
     import torch
     import torch.utils.cpp_extension as ce
@@ -35,8 +44,7 @@ def build(verbose: bool = True) -> str:
     libs = ce.library_paths(device_type="cuda")
     abi = "1" if torch._C._GLIBCXX_USE_CXX11_ABI else "0"
 
-    newest_src = max(os.path.getmtime(s) for s in SRC)
-    if os.path.exists(OUT) and os.path.getmtime(OUT) > newest_src:
+    if not is_stale(OUT, SRC + glob.glob(os.path.join(REPO, "csrc", "*.h"))):
         if verbose:
             print(f"[build_ext] up to date: {OUT}")
         return OUT
