@@ -216,7 +216,20 @@ void bin_features(torch::Tensor out, torch::Tensor x, torch::Tensor edges) {
 
 // ---------------------------------------------------------------------------
 // hist_build
-//   grid = (row_chunks, feature_groups); LDS histogram [FG][B][CELLS] u64.
+//   grid = (row_chunks, feature_groups); LDS histogram of FG*B*CELLS u64.
+//
+//   LDS LAYOUT (tools/probe_hist5.hip + profiles/hist_layout.md): an 8-byte
+//   LDS atomic is serviced in 4 groups of 16 contiguous lanes over 16 bank
+//   pairs, one extra cycle per extra address on a busy pair.  With cells
+//   [f][b][c] and every lane on the same feature the pair is b mod 16 —
+//   16 random bins into 16 pairs, 3.07 deep on average (the 67 %
+//   SQ_LDS_BANK_CONFLICT share).  The vectorised path (full groups of FG in
+//   {16, 32, 64}) therefore keeps cells BIN-MAJOR, [c][b][f], so the pair is
+//   f mod 16 whatever the bin, and lane l walks the 16 features of a piece
+//   rotated by l % 16: 16 contiguous lanes always hit 16 different pairs
+//   (probe: 9.1 vs 4.5 adds/clk/CU).  The byte-wise fallback (ragged or
+//   small groups) has all lanes on one feature, where bin-major would be a
+//   16-way conflict; it keeps [f][b][c].
 //
 //   KEY gfx950 design point (measured, tools/probe_hist2.hip +
 //   profiles/r01_hist_probe.md): LDS f32 atomicAdd (ds_add_f32) runs ~13x
@@ -243,7 +256,26 @@ void bin_features(torch::Tensor out, torch::Tensor x, torch::Tensor edges) {
 //   atomics into their slot of the staging buffer.
 // ---------------------------------------------------------------------------
 
-template <int DC, int NC>
+// rotate the 16 bytes of a bins piece right by lam bytes: byte p of the
+// result is byte (p + lam) % 16 of the input.  A dword rotate by lam >> 2
+// (two levels of selects) and a funnel shift by lam & 3 bytes, so the bytes
+// are still extracted with compile-time indices (no dynamic register index).
+__device__ inline void rotate_piece(unsigned (&w)[4], int lam) {
+  const bool r1 = lam & 4, r2 = lam & 8;
+  const unsigned a0 = r1 ? w[1] : w[0], a1 = r1 ? w[2] : w[1],
+                 a2 = r1 ? w[3] : w[2], a3 = r1 ? w[0] : w[3];
+  const unsigned b0 = r2 ? a2 : a0, b1 = r2 ? a3 : a1, b2 = r2 ? a0 : a2,
+                 b3 = r2 ? a1 : a3;
+  const unsigned t = lam & 3;
+  w[0] = __builtin_amdgcn_alignbyte(b1, b0, t);
+  w[1] = __builtin_amdgcn_alignbyte(b2, b1, t);
+  w[2] = __builtin_amdgcn_alignbyte(b3, b2, t);
+  w[3] = __builtin_amdgcn_alignbyte(b0, b3, t);
+}
+
+// BM (bin-major) is the vectorised path: every feature group is a full
+// FG in {16, 32, 64} features.  !BM is the byte-wise fallback.
+template <int DC, int NC, bool BM>
 __global__ void hist_build_kernel(
     float* __restrict__ out,            // [n_nodes, F, B, C]
     long long* __restrict__ stage,      // [n_multi, F, B, C] i64 (multi-chunk)
@@ -270,11 +302,16 @@ __global__ void hist_build_kernel(
   for (int i = threadIdx.x; i < lds_cells; i += blockDim.x) lds64[i] = 0ull;
   __syncthreads();
 
-  // bins rows are read FG bytes at a time in 16-B uint4 pieces when the
-  // group is 16-aligned and fully inside the row
-  const bool vec = (FG == 16 || FG == 32 || FG == 64) && (f0 + FG <= F) &&
-                   ((F % FG) == 0);
+  // BM: the host's FG choice gives FG <= 64 / 32 / 16 for CELLS 1 / 2 / >= 3
+  constexpr int MAXNH = CELLS == 1 ? 4 : (CELLS == 2 ? 2 : 1);
   const int nh = FG >> 4;
+  const int lam = threadIdx.x & 15;
+  const int bshift = 31 - __clz(FG) + 3;      // log2(FG * 8)
+  const unsigned plane = (unsigned)B * FG * 8;  // bytes per cell plane
+  // BM: byte offset of the feature that byte p of a rotated piece holds
+  unsigned foff[16];
+#pragma unroll
+  for (int p = 0; p < 16; ++p) foff[p] = ((p + lam) & 15) * 8;
 
   for (int i = threadIdx.x; i < len; i += blockDim.x) {
     const int r = identity_rows ? start + i : row_idx[start + i];
@@ -293,21 +330,31 @@ __global__ void hist_build_kernel(
       const int iv = __float2int_rn(g[DC + c] * scales[DC + c]);
       addend[c] |= (unsigned)iv;
     }
-    if (vec) {
-      for (int hh = 0; hh < nh; ++hh) {
-        const uint4 bv = *reinterpret_cast<const uint4*>(
-            bins + (int64_t)r * F + f0 + 16 * hh);
-        const unsigned w[4] = {bv.x, bv.y, bv.z, bv.w};
+    if constexpr (BM) {
+      // the row's FG bytes in 16-B uint4 pieces; at step p of piece hh this
+      // lane bumps feature 16*hh + (p + lam) % 16, so any 16 contiguous
+      // lanes hit 16 different bank pairs whatever their bins are
+      const uint8_t* br = bins + (int64_t)r * F + f0;
+      uint4 bv[MAXNH];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+      for (int hh = 0; hh < MAXNH; ++hh) {
+        bv[hh] = make_uint4(0, 0, 0, 0);
+        if (hh < nh) bv[hh] = *reinterpret_cast<const uint4*>(br + 16 * hh);
+      }
+      char* base = reinterpret_cast<char*>(lds64);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int b = (w[q] >> (8 * j)) & 0xff;
-            unsigned long long* cell =
-                lds64 + (((16 * hh + q * 4 + j) * B) + b) * CELLS;
+      for (int hh = 0; hh < MAXNH; ++hh) {
+        if (hh >= nh) break;
+        unsigned w[4] = {bv[hh].x, bv[hh].y, bv[hh].z, bv[hh].w};
+        rotate_piece(w, lam);
 #pragma unroll
-            for (int c = 0; c < CELLS; ++c) atomicAdd(cell + c, addend[c]);
-          }
+        for (int p = 0; p < 16; ++p) {
+          const unsigned b = (w[p >> 2] >> (8 * (p & 3))) & 0xff;
+          char* cell = base + ((b << bshift) + foff[p]) + hh * 128;
+#pragma unroll
+          for (int c = 0; c < CELLS; ++c)
+            atomicAdd(reinterpret_cast<unsigned long long*>(cell + c * plane),
+                      addend[c]);
         }
       }
     } else {
@@ -327,38 +374,52 @@ __global__ void hist_build_kernel(
   // into the i64 staging buffer — integer atomics are order-independent,
   // so histograms stay bitwise deterministic across runs (decode kernel
   // below converts once at the end).
-  if (slot < 0) {
-    float* dst = out + (((int64_t)node * F + f0) * B) * C;
-    for (int i = threadIdx.x; i < nf * B; i += blockDim.x) {
-      const int f = i / B, b = i - f * B;
-      const unsigned long long* cell = lds64 + ((f * B) + b) * CELLS;
-      float* o = dst + ((int64_t)f * B + b) * C;
+  // cell c of (f, b) is cell[c * cstride]
+  auto flush_cell = [&](int f, int b, const unsigned long long* cell,
+                        int cstride) {
+    if (slot < 0) {
+      float* o = out + (((int64_t)node * F + f0 + f) * B + b) * C;
 #pragma unroll
       for (int d = 0; d < DC; ++d)
-        o[d] = (float)(int)(unsigned)(cell[d] >> 32) / scales[d];
+        o[d] = (float)(int)(unsigned)(cell[d * cstride] >> 32) / scales[d];
 #pragma unroll
       for (int c = 0; c < NC; ++c)
-        o[DC + c] =
-            (float)(int)(unsigned)(cell[c] & 0xFFFFFFFFull) / scales[DC + c];
-    }
-  } else {
-    long long* sdst = stage + (((int64_t)slot * F + f0) * B) * C;
-    for (int i = threadIdx.x; i < nf * B; i += blockDim.x) {
-      const int f = i / B, b = i - f * B;
-      const unsigned long long* cell = lds64 + ((f * B) + b) * CELLS;
-      long long* o = sdst + ((int64_t)f * B + b) * C;
+        o[DC + c] = (float)(int)(unsigned)(cell[c * cstride] & 0xFFFFFFFFull) /
+                    scales[DC + c];
+    } else {
+      long long* o = stage + (((int64_t)slot * F + f0 + f) * B + b) * C;
 #pragma unroll
       for (int d = 0; d < DC; ++d) {
-        const int v = (int)(unsigned)(cell[d] >> 32);
+        const int v = (int)(unsigned)(cell[d * cstride] >> 32);
         if (v) atomicAdd((unsigned long long*)(o + d),
                          (unsigned long long)(long long)v);
       }
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
-        const int v = (int)(unsigned)(cell[c] & 0xFFFFFFFFull);
+        const int v = (int)(unsigned)(cell[c * cstride] & 0xFFFFFFFFull);
         if (v) atomicAdd((unsigned long long*)(o + DC + c),
                          (unsigned long long)(long long)v);
       }
+    }
+  };
+  if constexpr (BM) {
+    // consecutive bins of a feature are FG*8 bytes apart here, one bank for
+    // a whole wave; walk tiles of 8 features x 8 bins per wave instead (8
+    // bank pairs per group of 16 lanes, 8-bin runs of out per feature)
+    constexpr int TBL = 3;           // log2 bins per tile
+    constexpr int TB = 1 << TBL, TF = 64 >> TBL;
+    const int nbt = (B + TB - 1) >> TBL;
+    const int n_tiles = (FG / TF) * nbt;
+    for (int i = threadIdx.x; i < n_tiles * 64; i += blockDim.x) {
+      const int t = i >> 6, l = i & 63;
+      const int ft = t / nbt, bt = t - ft * nbt;
+      const int f = ft * TF + (l >> TBL), b = bt * TB + (l & (TB - 1));
+      if (b < B) flush_cell(f, b, lds64 + b * FG + f, B * FG);
+    }
+  } else {
+    for (int i = threadIdx.x; i < nf * B; i += blockDim.x) {
+      const int f = i / B, b = i - f * B;
+      flush_cell(f, b, lds64 + ((f * B) + b) * CELLS, 1);
     }
   }
 }
@@ -476,19 +537,30 @@ int64_t hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
   }
 
   auto stream = at::hip::getCurrentHIPStream();
-#define HB_LAUNCH(DD, NNN)                                                   \
+  // full 16-aligned groups take the vectorised bin-major kernel (FG <= 64 /
+  // 32 / 16 for CELLS 1 / 2 / >= 3 by the choice above, as it assumes)
+  const bool bin_major =
+      (FG == 16 || FG == 32 || FG == 64) && (F % FG) == 0;
+  TORCH_CHECK(!bin_major || FG <= (CELLS == 1 ? 64 : (CELLS == 2 ? 32 : 16)),
+              "hist_build: FG ", FG, " too wide for CELLS ", CELLS);
+#define HB_LAUNCH_L(DD, NNN, BM)                                             \
   do {                                                                       \
     if (lds_bytes > 65536)                                                   \
       (void)hipFuncSetAttribute(                                             \
-          reinterpret_cast<const void*>(&hist_build_kernel<DD, NNN>),        \
+          reinterpret_cast<const void*>(&hist_build_kernel<DD, NNN, BM>),    \
           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);       \
-    hipLaunchKernelGGL((hist_build_kernel<DD, NNN>),                         \
+    hipLaunchKernelGGL((hist_build_kernel<DD, NNN, BM>),                     \
                        dim3(plan.n_chunks, n_groups), dim3(threads),         \
                        lds_bytes, stream, out.data_ptr<float>(), stage_ptr,  \
                        bins.data_ptr<uint8_t>(),                             \
                        gh.data_ptr<float>(), row_idx.data_ptr<int>(),        \
                        chunks.data_ptr<int>(), F, B, FG, CH,                 \
                        identity_rows ? 1 : 0);                               \
+  } while (0)
+#define HB_LAUNCH(DD, NNN)                                                   \
+  do {                                                                       \
+    if (bin_major) HB_LAUNCH_L(DD, NNN, true);                               \
+    else HB_LAUNCH_L(DD, NNN, false);                                        \
   } while (0)
   const int key = D * 10 + NN;
   switch (key) {
@@ -508,6 +580,7 @@ int64_t hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
     default: TORCH_CHECK(false, "hist_build: unsupported D/NN ", D, "/", NN);
   }
 #undef HB_LAUNCH
+#undef HB_LAUNCH_L
   if (n_multi) {
     auto nodes = h2d_async(plan.multi_nodes.data(), (size_t)n_multi * 4,
                            kSlotHistNodes, bins.device());
