@@ -7,9 +7,11 @@
 // grid of ~resident-blocks x oversubscription (SEA_HIST_OVERSUB overrides),
 // floored at 4096 rows and capped at 2^20 so a chunk's fixed-point sums and
 // row counts keep their 2^30 headroom.  A node that fits one chunk flushes
-// with plain stores (slot -1); a multi-chunk node gets a dense i64 staging
-// slot that its chunks add into and a decode pass converts.  Every node gets
-// at least one record, so a zero-row node's block writes its zeros itself.
+// with plain stores (slot -1); a multi-chunk node gets a staging slot that a
+// second pass sums over the node's chunks and converts.  The records of a
+// node are consecutive, so a slot is named by its first record and record
+// count.  Every node gets at least one record, so a zero-row node's block
+// writes its zeros itself.
 #pragma once
 
 #include <algorithm>
@@ -29,6 +31,8 @@ struct HistPlan {
   // (node, start, len, slot, col0)
   std::vector<int> table;
   std::vector<int> multi_nodes;  // node id of each staging slot
+  std::vector<int> slot_first;   // first chunk record of each staging slot
+  std::vector<int> slot_count;   // its number of (consecutive) records
 };
 
 inline HistPlan plan_hist_chunks(const int64_t* offs, int n_nodes,
@@ -75,6 +79,8 @@ inline HistPlan plan_hist_chunks(const int64_t* offs, int n_nodes,
     if (e - s > p.chunk_rows) {
       slot = (int)p.multi_nodes.size();
       p.multi_nodes.push_back(nd);
+      p.slot_first.push_back((int)((p.table.size() - header_words) / 5));
+      p.slot_count.push_back((int)((e - s + p.chunk_rows - 1) / p.chunk_rows));
     }
     int64_t c = s;
     do {

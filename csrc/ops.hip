@@ -251,9 +251,19 @@ void bin_features(torch::Tensor out, torch::Tensor x, torch::Tensor edges) {
 //   GBMClassifier.scala:377-411 parallel futures) interleaves per-tree
 //   channel groups [g_t, h_t(, cnt_t)] and sets col0 = tree * C, so one
 //   launch histograms every active node of every tree.
-//   Flush converts back to f32 into out [n_nodes, F, B, C]; single-chunk
-//   nodes (stage_slot < 0) use plain stores, multi-chunk nodes integer
-//   atomics into their slot of the staging buffer.
+//   ``gh_pos``: gh is the compact [M, CH] matrix gather_ranges_gh built
+//   alongside row_idx, so position start + i reads gh row start + i (a
+//   stream) while bins are still fetched through row_idx.
+//   Flush, single-chunk nodes (stage_slot < 0): convert back to f32 straight
+//   into out [n_nodes, F, B, C] with plain stores, 16 B per lane for C = 2.
+//   Multi-chunk nodes of the one-cell bin-major kernel: each block copies
+//   its LDS image as it stands into its own slab of ``partial``
+//   ([multi records, n_groups, FG*B] u64); hist_reduce_kernel sums a node's
+//   slabs in int64 and converts.  After the chunk records the table carries
+//   (node, first record, record count, first slab) per staging slot.
+//   Kernels of two and more cells, the byte-wise fallback and a partial
+//   buffer over its size bound add integer atomics into the slot of the i64
+//   ``stage`` buffer instead, which hist_decode_kernel converts.
 // ---------------------------------------------------------------------------
 
 // rotate the 16 bytes of a bins piece right by lam bytes: byte p of the
@@ -273,17 +283,25 @@ __device__ inline void rotate_piece(unsigned (&w)[4], int lam) {
   w[3] = __builtin_amdgcn_alignbyte(b0, b3, t);
 }
 
+// Which instantiations flush multi-chunk nodes as slabs: the one-cell kernel
+// (C = 2, the flagship).  With two cells the slabs measured slower than the
+// staged atomics on three hist_bench rows (profiles/hist_flush.md), so two
+// and more cells keep the atomics.
+template <int DC, int NC>
+constexpr bool kHistSlabFlush = (DC > NC ? DC : NC) == 1;
+
 // BM (bin-major) is the vectorised path: every feature group is a full
 // FG in {16, 32, 64} features.  !BM is the byte-wise fallback.
 template <int DC, int NC, bool BM>
 __global__ void hist_build_kernel(
     float* __restrict__ out,            // [n_nodes, F, B, C]
-    long long* __restrict__ stage,      // [n_multi, F, B, C] i64 (multi-chunk)
+    long long* __restrict__ stage,      // [n_multi, F, B, C] i64, or null
+    unsigned long long* __restrict__ partial,  // LDS-image slabs (BM), or null
     const uint8_t* __restrict__ bins,   // [N, F]
-    const float* __restrict__ gh,       // [N, CH]
+    const float* __restrict__ gh,       // [N, CH], or [M, CH] with gh_pos
     const int* __restrict__ row_idx,    // [M]
-    const int* __restrict__ chunks,     // [2*C + n_chunks*5] (scales first)
-    int F, int B, int FG, int CH, int identity_rows) {
+    const int* __restrict__ chunks,     // scales, chunk records, slot records
+    int F, int B, int FG, int CH, int identity_rows, int gh_pos) {
   constexpr int C = DC + NC;
   constexpr int CELLS = DC > NC ? DC : NC;
   extern __shared__ unsigned long long lds64[];  // FG * B * CELLS
@@ -315,7 +333,7 @@ __global__ void hist_build_kernel(
 
   for (int i = threadIdx.x; i < len; i += blockDim.x) {
     const int r = identity_rows ? start + i : row_idx[start + i];
-    const float* g = gh + (int64_t)r * CH + col0;
+    const float* g = gh + (int64_t)(gh_pos ? start + i : r) * CH + col0;
     // quantize once per row, pack one u64 addend per cell
     unsigned long long addend[CELLS];
 #pragma unroll
@@ -403,6 +421,59 @@ __global__ void hist_build_kernel(
     }
   };
   if constexpr (BM) {
+    if constexpr (kHistSlabFlush<DC, NC>) {
+      if (slot >= 0 && partial) {
+        // multi-chunk node: the LDS image goes as it stands, 16 B per lane,
+        // into this block's slab; hist_reduce_kernel sums the node's slabs.
+        // slot record = (node, first record, record count, first slab)
+        const int* srec = chunks + 2 * C + (int)gridDim.x * 5 + slot * 4;
+        const int64_t slab =
+            (int64_t)(srec[3] + (int)blockIdx.x - srec[1]) * gridDim.y + fg;
+        uint4* dst = reinterpret_cast<uint4*>(partial + slab * lds_cells);
+        const uint4* img = reinterpret_cast<const uint4*>(lds64);
+        for (int i = threadIdx.x; i < lds_cells / 2; i += blockDim.x)
+          dst[i] = img[i];
+        return;
+      }
+    }
+    // single-chunk node, C = 2: a lane converts two adjacent bins of one
+    // feature and stores them as one float4; a wave covers 8 features x 16
+    // bins, 128 contiguous bytes of out per feature.  (The same with 4 bins
+    // = three float4 per lane for C = 3 measured slower than the 8 x 8 tile,
+    // profiles/hist_flush.md, so C = 3 stays on the tile.)
+    constexpr int NB = C == 2 ? 2 : 1;
+    if (NB > 1 && slot < 0 && B % NB == 0 &&  // NB == 1: never taken
+        (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+      const int nbt = (B + 8 * NB - 1) / (8 * NB);
+      const int n_tiles = (FG >> 3) * nbt;
+      for (int i = threadIdx.x; i < n_tiles * 64; i += blockDim.x) {
+        const int t = i >> 6, l = i & 63;
+        const int ft = t / nbt, bt = t - ft * nbt;
+        const int f = ft * 8 + (l >> 3), b = (bt * 8 + (l & 7)) * NB;
+        if (b >= B) continue;
+        float v[NB * C];
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+          const unsigned long long* cell = lds64 + (b + k) * FG + f;
+#pragma unroll
+          for (int d = 0; d < DC; ++d)
+            v[k * C + d] =
+                (float)(int)(unsigned)(cell[d * B * FG] >> 32) / scales[d];
+#pragma unroll
+          for (int c = 0; c < NC; ++c)
+            v[k * C + DC + c] =
+                (float)(int)(unsigned)(cell[c * B * FG] & 0xFFFFFFFFull) /
+                scales[DC + c];
+        }
+        float4* o = reinterpret_cast<float4*>(
+            out + (((int64_t)node * F + f0 + f) * B + b) * C);
+#pragma unroll
+        for (int q = 0; q < NB * C / 4; ++q)
+          o[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2],
+                             v[4 * q + 3]);
+      }
+      return;
+    }
     // consecutive bins of a feature are FG*8 bytes apart here, one bank for
     // a whole wave; walk tiles of 8 features x 8 bins per wave instead (8
     // bank pairs per group of 16 lanes, 8-bin runs of out per feature)
@@ -447,12 +518,64 @@ void launch_hist_decode(float* out, const long long* stage, const int* nodes,
                      stream, out, stage, nodes, scales, FBC, C);
 }
 
-// Returns the number of multi-chunk nodes.
+// Sum the LDS-image slabs of each multi-chunk node of the bin-major path and
+// convert: out[node, f, b, :] = (float)(int64 sum over the node's records of
+// the fields of partial[slab, group of f][cell][b][f % FG]) / scale.  The
+// integers and the divide are those of the staged-atomics path, and integer
+// sums have no order, so both give the same bits.  Lanes walk the flush's
+// 8 features x 8 bins tile: 64-byte runs on both sides.
+__global__ void hist_reduce_kernel(
+    float* __restrict__ out,                         // [n_nodes, F, B, C]
+    const unsigned long long* __restrict__ partial,  // slabs
+    const int* __restrict__ slots,   // [n_multi, 4] node, first, count, slab
+    const float* __restrict__ scales,  // [C]
+    int F, int B, int FG, int DC, int NC) {
+  const int* srec = slots + blockIdx.y * 4;
+  const int node = srec[0], count = srec[2];
+  const int C = DC + NC, CELLS = DC > NC ? DC : NC;
+  const int n_groups = F / FG;
+  const int nbt = (B + 7) >> 3;
+  const int group_tiles = (FG >> 3) * nbt;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int t = i >> 6, l = i & 63;
+  const int g = t / group_tiles;
+  if (g >= n_groups) return;
+  const int tt = t - g * group_tiles;
+  const int ft = tt / nbt, bt = tt - ft * nbt;
+  const int f = ft * 8 + (l >> 3), b = bt * 8 + (l & 7);
+  if (b >= B) return;
+  const int64_t plane = (int64_t)B * FG;
+  const int64_t kstride = (int64_t)n_groups * plane * CELLS;
+  const unsigned long long* p =
+      partial + ((int64_t)srec[3] * n_groups + g) * plane * CELLS + b * FG + f;
+  float* o = out + (((int64_t)node * F + g * FG + f) * B + b) * C;
+  for (int c = 0; c < CELLS; ++c) {
+    long long hi = 0, lo = 0;
+#pragma unroll 4
+    for (int k = 0; k < count; ++k) {
+      const unsigned long long v = p[k * kstride + c * plane];
+      hi += (int)(unsigned)(v >> 32);
+      lo += (int)(unsigned)(v & 0xFFFFFFFFull);
+    }
+    if (c < DC) o[c] = (float)hi / scales[c];
+    if (c < NC) o[DC + c] = (float)lo / scales[DC + c];
+  }
+}
+
+// The partial buffer of the slab flush is at most (records of multi-chunk
+// nodes) x n_groups x lds_bytes; the planner keeps the records near one
+// resident grid (32 MiB at 10M x 256 x 256 bins), but rows past 2^26 or very
+// wide rows can outgrow that.  Above this bound the launch falls back to the
+// staged atomics.
+constexpr int64_t kHistPartialMaxBytes = (int64_t)1 << 30;
+
+// Returns the number of multi-chunk nodes.  ``gh_by_position``: gh is the
+// compact [row_idx.numel(), CH] matrix of gather_ranges_gh, read by position.
 int64_t hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
                    torch::Tensor row_idx, torch::Tensor node_offsets,
                    int64_t num_bins, int64_t d_dims, torch::Tensor max_abs,
                    bool identity_rows, torch::Tensor node_col0,
-                   int64_t c_per_node) {
+                   int64_t c_per_node, bool gh_by_position) {
   CHECK_GPU(out); CHECK_GPU(bins); CHECK_GPU(gh); CHECK_GPU(row_idx);
   CHECK_CONTIG(out); CHECK_CONTIG(bins); CHECK_CONTIG(gh); CHECK_CONTIG(row_idx);
   TORCH_CHECK(!node_offsets.is_cuda(), "node_offsets stays on host");
@@ -478,6 +601,9 @@ int64_t hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
   TORCH_CHECK(max_abs.numel() == C, "max_abs must have C entries");
   TORCH_CHECK(out.numel() == (int64_t)n_nodes * F * B * C,
               "out must be [n_nodes, F, B, C]");
+  TORCH_CHECK(!gh_by_position ||
+                  (!identity_rows && gh.size(0) == row_idx.numel()),
+              "gh_by_position: gh must have one row per row_idx entry");
   if (n_nodes == 0 || F == 0) return 0;
   const int CELLS = std::max(D, NN);
 
@@ -515,6 +641,28 @@ int64_t hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
       identity_rows ? bins.size(0) : row_idx.numel(), CH - C + 1, lds_bytes,
       n_groups, 2 * C);
 
+  // full 16-aligned groups take the vectorised bin-major kernel (FG <= 64 /
+  // 32 / 16 for CELLS 1 / 2 / >= 3 by the choice above, as it assumes)
+  const bool bin_major =
+      (FG == 16 || FG == 32 || FG == 64) && (F % FG) == 0;
+  TORCH_CHECK(!bin_major || FG <= (CELLS == 1 ? 64 : (CELLS == 2 ? 32 : 16)),
+              "hist_build: FG ", FG, " too wide for CELLS ", CELLS);
+
+  // staging slot records after the chunk records: (node, first record,
+  // record count, first slab); a node's slabs follow its records' order
+  const int n_multi = (int)plan.multi_nodes.size();
+  const size_t slots_at = plan.table.size();
+  int64_t n_slabs = 0;
+  for (int s = 0; s < n_multi; ++s) {
+    const int rec[4] = {plan.multi_nodes[s], plan.slot_first[s],
+                        plan.slot_count[s], (int)n_slabs};
+    plan.table.insert(plan.table.end(), rec, rec + 4);
+    n_slabs += plan.slot_count[s];
+  }
+  const int64_t partial_bytes = n_slabs * n_groups * (int64_t)lds_bytes;
+  const bool use_partial = bin_major && CELLS == 1 /* kHistSlabFlush */ &&
+                           n_multi && partial_bytes <= kHistPartialMaxBytes;
+
   // header: per-channel quantization scales
   auto max_abs_f = max_abs.to(torch::kFloat32).contiguous();
   auto ma = max_abs_f.accessor<float, 1>();
@@ -525,24 +673,25 @@ int64_t hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
                           kSlotHistChunks, bins.device())
                     .view(torch::kInt32);
 
-  // i64 integer staging for multi-chunk nodes (order-independent flush =>
-  // bitwise-deterministic histograms)
-  const int n_multi = (int)plan.multi_nodes.size();
-  torch::Tensor stage;
+  // multi-chunk nodes: every block's LDS image in its own slab (no fill
+  // needed: each slab is written whole), or the zero-filled i64 staging the
+  // atomics add into.  Integer sums either way, so histograms are bitwise
+  // deterministic.
+  torch::Tensor stage, partial;
   long long* stage_ptr = nullptr;
-  if (n_multi) {
+  unsigned long long* partial_ptr = nullptr;
+  if (use_partial) {
+    partial = torch::empty({partial_bytes / 8},
+                           out.options().dtype(torch::kInt64));
+    partial_ptr =
+        reinterpret_cast<unsigned long long*>(partial.data_ptr<int64_t>());
+  } else if (n_multi) {
     stage = torch::zeros({(int64_t)n_multi, (int64_t)F, (int64_t)B, (int64_t)C},
                          out.options().dtype(torch::kInt64));
     stage_ptr = reinterpret_cast<long long*>(stage.data_ptr<int64_t>());
   }
 
   auto stream = at::hip::getCurrentHIPStream();
-  // full 16-aligned groups take the vectorised bin-major kernel (FG <= 64 /
-  // 32 / 16 for CELLS 1 / 2 / >= 3 by the choice above, as it assumes)
-  const bool bin_major =
-      (FG == 16 || FG == 32 || FG == 64) && (F % FG) == 0;
-  TORCH_CHECK(!bin_major || FG <= (CELLS == 1 ? 64 : (CELLS == 2 ? 32 : 16)),
-              "hist_build: FG ", FG, " too wide for CELLS ", CELLS);
 #define HB_LAUNCH_L(DD, NNN, BM)                                             \
   do {                                                                       \
     if (lds_bytes > 65536)                                                   \
@@ -552,10 +701,10 @@ int64_t hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
     hipLaunchKernelGGL((hist_build_kernel<DD, NNN, BM>),                     \
                        dim3(plan.n_chunks, n_groups), dim3(threads),         \
                        lds_bytes, stream, out.data_ptr<float>(), stage_ptr,  \
-                       bins.data_ptr<uint8_t>(),                             \
+                       partial_ptr, bins.data_ptr<uint8_t>(),                \
                        gh.data_ptr<float>(), row_idx.data_ptr<int>(),        \
                        chunks.data_ptr<int>(), F, B, FG, CH,                 \
-                       identity_rows ? 1 : 0);                               \
+                       identity_rows ? 1 : 0, gh_by_position ? 1 : 0);       \
   } while (0)
 #define HB_LAUNCH(DD, NNN)                                                   \
   do {                                                                       \
@@ -581,7 +730,15 @@ int64_t hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
   }
 #undef HB_LAUNCH
 #undef HB_LAUNCH_L
-  if (n_multi) {
+  if (use_partial) {
+    const int64_t lanes = (int64_t)n_groups * (FG >> 3) * ((B + 7) >> 3) * 64;
+    hipLaunchKernelGGL(hist_reduce_kernel,
+                       dim3((unsigned)ceil_div(lanes, 256), n_multi),
+                       dim3(256), 0, stream, out.data_ptr<float>(),
+                       partial_ptr, chunks.data_ptr<int>() + slots_at,
+                       reinterpret_cast<const float*>(chunks.data_ptr<int>()),
+                       F, B, FG, D, NN);
+  } else if (n_multi) {
     auto nodes = h2d_async(plan.multi_nodes.data(), (size_t)n_multi * 4,
                            kSlotHistNodes, bins.device());
     launch_hist_decode(out.data_ptr<float>(), stage_ptr,
@@ -999,6 +1156,31 @@ __global__ void gather_ranges_kernel(
   }
 }
 
+// gather_ranges that also brings the rows' gradients along: gh_out[p, :] =
+// gh[out[p], col0[s] : col0[s] + C] for position p of range s, so the
+// histogram kernel streams gh by position instead of gathering it once per
+// feature group
+__global__ void gather_ranges_gh_kernel(
+    int* __restrict__ out,               // [total]
+    float* __restrict__ gh_out,          // [total, C]
+    const int* __restrict__ src,
+    const float* __restrict__ gh,        // [N, CH]
+    const long long* __restrict__ seg,   // [cum n_segs+1, starts, col0]
+    int n_segs, long long total, int C, int CH) {
+  const long long* cum = seg;
+  const long long* starts = seg + n_segs + 1;
+  const long long* col0 = starts + n_segs;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       p < total; p += stride) {
+    const int s = seg_of(cum, n_segs, p);
+    const int r = src[starts[s] + (p - cum[s])];
+    out[p] = r;
+    const float* g = gh + (long long)r * CH + col0[s];
+    for (int c = 0; c < C; ++c) gh_out[p * C + c] = g[c];
+  }
+}
+
 __global__ void leaf_scatter_kernel(
     float* __restrict__ tp,              // [N, T] row-major
     const int* __restrict__ row_idx,     // level row arena
@@ -1040,6 +1222,50 @@ void gather_ranges(torch::Tensor out, torch::Tensor src,
   hipLaunchKernelGGL(gather_ranges_kernel, dim3(blocks), dim3(256), 0, stream,
                      out.data_ptr<int>(), src.data_ptr<int>(),
                      (const long long*)seg_b.data_ptr(), n_segs, total);
+}
+
+// src rows are trusted like hist_build's row_idx; the column window
+// [col0, col0 + C) of every range is checked against gh's width here
+void gather_ranges_gh(torch::Tensor out, torch::Tensor gh_out,
+                      torch::Tensor src, torch::Tensor gh,
+                      torch::Tensor starts, torch::Tensor lens,
+                      torch::Tensor col0) {
+  CHECK_GPU(out); CHECK_GPU(gh_out); CHECK_GPU(src); CHECK_GPU(gh);
+  CHECK_CONTIG(out); CHECK_CONTIG(gh_out); CHECK_CONTIG(src); CHECK_CONTIG(gh);
+  TORCH_CHECK(gh.dim() == 2 && gh_out.dim() == 2 &&
+                  gh_out.size(0) == out.numel(),
+              "gather_ranges_gh: gh_out must be [out.numel(), C]");
+  const int n_segs = (int)starts.numel();
+  const long long total = out.numel();
+  const int C = (int)gh_out.size(1), CH = (int)gh.size(1);
+  TORCH_CHECK(lens.numel() == n_segs && col0.numel() == n_segs,
+              "gather_ranges_gh: one len and col0 per range");
+  if (n_segs == 0 || total == 0) return;
+  auto st = starts.accessor<int64_t, 1>();
+  auto ln = lens.accessor<int64_t, 1>();
+  auto c0 = col0.accessor<int64_t, 1>();
+  std::vector<long long> seg_v(3 * n_segs + 1);
+  seg_v[0] = 0;
+  for (int i = 0; i < n_segs; ++i) {
+    TORCH_CHECK(ln[i] >= 0 && st[i] >= 0 && st[i] + ln[i] <= src.numel(),
+                "gather_ranges_gh: range outside src");
+    TORCH_CHECK(c0[i] >= 0 && c0[i] + C <= CH,
+                "gather_ranges_gh: col0 outside gh");
+    seg_v[i + 1] = seg_v[i] + ln[i];
+    seg_v[n_segs + 1 + i] = st[i];
+    seg_v[2 * n_segs + 1 + i] = c0[i];
+  }
+  TORCH_CHECK(seg_v[n_segs] == total,
+              "gather_ranges_gh: lens sum != out size");
+  auto seg_b = h2d_async(seg_v.data(), seg_v.size() * 8, kSlotGatherSegs,
+                         src.device());
+  auto stream = at::hip::getCurrentHIPStream();
+  const int blocks =
+      (int)std::min<long long>(8192, ceil_div(total, (long long)1024));
+  hipLaunchKernelGGL(gather_ranges_gh_kernel, dim3(blocks), dim3(256), 0,
+                     stream, out.data_ptr<int>(), gh_out.data_ptr<float>(),
+                     src.data_ptr<int>(), gh.data_ptr<float>(),
+                     (const long long*)seg_b.data_ptr(), n_segs, total, C, CH);
 }
 
 void leaf_scatter(torch::Tensor tp, torch::Tensor row_idx,
@@ -1776,9 +2002,32 @@ std::tuple<int64_t, torch::Tensor, torch::Tensor> hist_plan_debug(
   return {plan.chunk_rows, chunks, multi};
 }
 
+// the same plan's staging slots: (first record, record count) per slot, in
+// the order of _hist_plan's multi_nodes
+std::tuple<torch::Tensor, torch::Tensor> hist_plan_slots_debug(
+    torch::Tensor node_offsets, torch::Tensor node_col0, int64_t row_bound,
+    int64_t col_bound, int64_t lds_bytes, int64_t n_groups) {
+  auto offs = node_offsets.to(torch::kInt64).contiguous();
+  auto col0 = node_col0.to(torch::kInt32).contiguous();
+  const int n_nodes = (int)offs.numel() - 1;
+  TORCH_CHECK(col0.numel() == 0 || col0.numel() == n_nodes,
+              "node_col0 must be empty or have one entry per node");
+  HistPlan plan = plan_hist_chunks(
+      offs.data_ptr<int64_t>(), n_nodes,
+      col0.numel() ? col0.data_ptr<int>() : nullptr, row_bound,
+      (int)col_bound, (size_t)lds_bytes, (int)n_groups, 0);
+  auto i32 = torch::TensorOptions().dtype(torch::kInt32);
+  return {torch::tensor(plan.slot_first, i32),
+          torch::tensor(plan.slot_count, i32)};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("_hist_plan", &hist_plan_debug,
         "host-side chunk plan of the histogram kernels (no device)");
+  m.def("_hist_plan_slots", &hist_plan_slots_debug,
+        "first record and record count of each staging slot of _hist_plan");
+  m.def("gather_ranges_gh", &gather_ranges_gh,
+        "gather_ranges plus the compact gh rows of the gathered rows");
   m.def("logreg_loss_grad", &logreg_loss_grad,
         "single-pass fused logistic loss+gradient");
   m.def("logreg_fused_supported", &logreg_fused_supported);
@@ -1786,7 +2035,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused best-split gain scan + argmax over node histograms");
   m.def("sample_weights", &sample_weights, "counter-based Poisson/Bernoulli row weights");
   m.def("bin_features", &bin_features, "quantile binning f32 -> u8");
-  m.def("hist_build", &hist_build, "LDS-staged node histograms");
+  m.def("hist_build", &hist_build, "LDS-staged node histograms",
+        py::arg("out"), py::arg("bins"), py::arg("gh"), py::arg("row_idx"),
+        py::arg("node_offsets"), py::arg("num_bins"), py::arg("d_dims"),
+        py::arg("max_abs"), py::arg("identity_rows"), py::arg("node_col0"),
+        py::arg("c_per_node"), py::arg("gh_by_position") = false);
   m.def("hist_build_class", &hist_build_class,
         "label-indexed node histograms for K-class gini trees");
   m.def("partition_rows", &partition_rows, "block-aggregated node partition");

@@ -837,14 +837,22 @@ def grow_forest(
                 lens = offsets[built_cpu + 1] - starts
                 b_off = torch.zeros(built_cpu.numel() + 1, dtype=torch.int64)
                 b_off[1:] = torch.cumsum(lens, 0)
-                build_rows = ops.gather_ranges(row_idx, starts, lens)
                 if class_mode:
+                    build_rows = ops.gather_ranges(row_idx, starts, lens)
                     bh = _class_hist(build_rows, b_off, node_tree[built_cpu])
                 else:
-                    col0_b = (node_tree[built_cpu] * C).to(torch.int32)
+                    # the pass that collects the built rows brings their
+                    # gradient columns along, so the histogram kernel
+                    # streams a compact [M, C] matrix by position instead
+                    # of gathering gh once per feature group
+                    build_rows, gh_b = ops.gather_ranges_gh(
+                        row_idx, gh, starts, lens, node_tree[built_cpu] * C,
+                        C,
+                    )
                     bh = ops.hist_build_forest(
-                        bins, gh, build_rows, b_off, col0_b, B, C, gh_max,
-                        d_dims=D,
+                        bins, gh_b, build_rows, b_off,
+                        torch.zeros(built_cpu.numel(), dtype=torch.int32),
+                        B, C, gh_max, d_dims=D, gh_by_position=True,
                     )
             hists, gain, feat, b, left_stats = _finish_level_split(
                 bh, _to_dev_async(built_cpu, device), hists,

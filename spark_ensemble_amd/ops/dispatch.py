@@ -147,10 +147,11 @@ _EMPTY_U8 = torch.empty(0, dtype=torch.uint8)
 
 
 def _hist_build_launch(m, bins, gh, row_idx, node_offsets, node_col0,
-                       num_bins, c_per_node, max_abs, d_dims, identity_rows):
+                       num_bins, c_per_node, max_abs, d_dims, identity_rows,
+                       gh_by_position=False):
     """Allocate ``out`` and run the native hist_build.  Every node's slice
-    is fully written by the kernel's flush or the staging decode (zero-row
-    nodes included), so ``out`` needs no zero fill."""
+    is fully written by the kernel's flush or the staging reduction
+    (zero-row nodes included), so ``out`` needs no zero fill."""
     out = torch.empty(
         node_offsets.numel() - 1, bins.shape[1], num_bins, c_per_node,
         dtype=torch.float32, device=bins.device,
@@ -159,13 +160,13 @@ def _hist_build_launch(m, bins, gh, row_idx, node_offsets, node_col0,
         out, bins, gh.contiguous(), row_idx.to(torch.int32),
         node_offsets.to(torch.int64).cpu().contiguous(), int(num_bins),
         int(d_dims), max_abs.to(torch.float32), bool(identity_rows),
-        node_col0, int(c_per_node),
+        node_col0, int(c_per_node), bool(gh_by_position),
     )
     return out
 
 
 def hist_build_forest(bins, gh, row_idx, node_offsets, node_col0, num_bins,
-                      c_per_node, max_abs, d_dims=1):
+                      c_per_node, max_abs, d_dims=1, gh_by_position=False):
     """Forest histogram build: gh is [N, CH] with contiguous per-node
     channel groups; node_col0[n] selects the base column node n
     accumulates (tree fusion: owning_tree * C; wide-gini chunking: the
@@ -173,15 +174,23 @@ def hist_build_forest(bins, gh, row_idx, node_offsets, node_col0, num_bins,
     tree in the level (the MI355X form of the reference's parallel
     per-class futures, GBMClassifier.scala:377-411).  ``max_abs`` is
     slot-wise ([c_per_node]): max over the corresponding column of every
-    group."""
+    group.  ``gh_by_position``: gh is the compact ``[len(row_idx), CH]``
+    matrix of ``gather_ranges_gh`` and entry i of row_idx reads gh row i."""
     if bins.is_cuda:
         m = _require_hip("hist_build")
         if m is not None:
             return _hist_build_launch(
                 m, bins, gh, row_idx, node_offsets,
                 node_col0.to(torch.int32).cpu().contiguous(), num_bins,
-                c_per_node, max_abs, d_dims, False,
+                c_per_node, max_abs, d_dims, False, gh_by_position,
             )
+    if gh_by_position:
+        # the reference indexes gh by row: bins gathered, rows = positions
+        pos = torch.arange(row_idx.numel(), device=row_idx.device)
+        return reference.hist_build_forest(
+            bins.index_select(0, row_idx.long()), gh, pos, node_offsets,
+            node_col0, num_bins, c_per_node
+        )
     return reference.hist_build_forest(
         bins, gh, row_idx, node_offsets, node_col0, num_bins, c_per_node
     )
@@ -371,6 +380,36 @@ def gather_ranges(src, starts, lens):
     if not segs:
         return torch.empty(0, dtype=src.dtype, device=src.device)
     return segs[0].clone() if len(segs) == 1 else torch.cat(segs)
+
+
+def gather_ranges_gh(src, gh, starts, lens, col0, c_per_node):
+    """``gather_ranges`` that brings the gradients along: returns the
+    gathered rows and the compact ``[M, c_per_node]`` matrix whose row i is
+    ``gh[rows[i], col0_j : col0_j + c_per_node]`` for the range j that
+    position i belongs to.  One gather per built row, in the pass that
+    already writes the rows; ``hist_build_forest(..., gh_by_position=True)``
+    then streams it.  starts/lens/col0 are small cpu tensors."""
+    C = int(c_per_node)
+    if src.is_cuda:
+        m = _require_hip("gather_ranges_gh")
+        if m is not None:
+            total = int(lens.sum())
+            out = torch.empty(total, dtype=torch.int32, device=src.device)
+            gh_out = torch.empty(total, C, dtype=torch.float32,
+                                 device=src.device)
+            m.gather_ranges_gh(out, gh_out, src, gh.contiguous(),
+                               starts.to(torch.int64), lens.to(torch.int64),
+                               col0.to(torch.int64))
+            return out, gh_out
+    rows = gather_ranges(src, starts, lens)
+    segs = [
+        gh[src[s:s + l].long(), c0:c0 + C]
+        for s, l, c0 in zip(starts.tolist(), lens.tolist(), col0.tolist())
+        if l > 0
+    ]
+    if not segs:
+        return rows, gh.new_empty(0, C)
+    return rows, torch.cat(segs)
 
 
 def leaf_scatter(tp, row_idx, starts, lens, tree, val):
