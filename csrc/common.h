@@ -64,6 +64,13 @@ int64_t hist_build_class(torch::Tensor out, torch::Tensor bins,
                          int64_t num_bins, int64_t num_classes, int64_t nn,
                          double w_max, bool identity_rows);
 
+// csrc/tree_contrib.hip
+void forest_contrib(torch::Tensor out, torch::Tensor x, torch::Tensor ranges,
+                    torch::Tensor path_off, torch::Tensor path_m,
+                    torch::Tensor path_v, torch::Tensor e_feat,
+                    torch::Tensor e_lo, torch::Tensor e_hi, torch::Tensor e_z,
+                    int64_t rows_per_tile, double scale);
+
 // csrc/linear.hip
 void logreg_loss_grad(torch::Tensor payload, torch::Tensor x, torch::Tensor y,
                       torch::Tensor w, torch::Tensor wmat, bool has_bias);

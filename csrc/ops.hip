@@ -2047,6 +2047,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("forest_predict", &forest_predict, "packed-forest weighted predict");
   m.def("forest_predict2", &forest_predict2,
         "LDS-staged tree-group-tiled forest predict");
+  m.def("forest_contrib", &forest_contrib,
+        "per-row feature contributions (TreeSHAP) of a packed forest");
   m.def("transpose_u8", &transpose_u8, "tiled u8 matrix transpose");
   m.def("gather_ranges", &gather_ranges,
         "one-pass concat of contiguous index ranges");

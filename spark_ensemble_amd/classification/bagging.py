@@ -227,6 +227,34 @@ class BaggingClassificationModel(
                 )
         return acc
 
+    def predictContrib(self, features: torch.Tensor) -> torch.Tensor:
+        """Per-row additive feature contributions ``[N, K, F + 1]`` of the
+        vote sums, one plane per class, in the original feature space
+        (path-dependent TreeSHAP, docs/contributions.md): column F is the
+        bias and plane k of every row sums to ``predictRaw[:, k]``.  Soft
+        and hard voting are both sums over leaves of the per-node leaf
+        transforms ``predictRaw`` packs, so both are explained exactly.
+        Raises ValueError for a member that is not a built-in
+        classification tree.  NaN features are not supported."""
+        from ..ensemble.utils import packed_forest_contrib
+        from ..models.tree import DecisionTreeClassificationModel
+
+        for i, m in enumerate(self._models):
+            if not isinstance(m, DecisionTreeClassificationModel):
+                raise ValueError(
+                    "predictContrib needs built-in classification tree "
+                    f"members; member {i} is a {type(m).__name__}"
+                )
+        soft = self.getVotingStrategy() == "soft"
+        mcount = len(self._models)
+        return packed_forest_contrib(
+            features.float(), self._models, [1.0] * mcount, [0] * mcount,
+            self._subspaces, self._num_classes,
+            vote="soft" if soft else "hard",
+            cache=self.__dict__.setdefault(
+                "_contrib_cache_soft" if soft else "_contrib_cache_hard", {}),
+        )
+
     def raw2probabilityInPlace(self, raw: torch.Tensor) -> torch.Tensor:
         raw /= len(self._models)
         return raw

@@ -592,6 +592,39 @@ class GBMClassificationModel(ProbabilisticClassificationModel, _GBMClassifierPar
             return torch.cat([-s, s], dim=1)
         return s
 
+    def predictContrib(self, features: torch.Tensor) -> torch.Tensor:
+        """Per-row additive feature contributions ``[N, dim, F + 1]`` of the
+        margins, one plane per loss dimension (path-dependent TreeSHAP,
+        docs/contributions.md): column F is the bias (the init raw value
+        goes there) and plane j of every row sums to ``_margins[:, j]``.
+        For ``dim > 1`` that is ``predictRaw``.  In the binary case
+        ``dim = 1`` and ``predictRaw = (-s, s)`` for the margin ``s``: class
+        1's contributions are plane 0 and class 0's are its negation.
+        Raises ValueError for a non-constant init or a stage that is not a
+        built-in tree.  NaN features are not supported."""
+        from ..ensemble.utils import packed_forest_contrib
+        from ..models.dummy import DummyClassificationModel
+
+        if not isinstance(self._init, DummyClassificationModel):
+            raise ValueError(
+                "predictContrib needs a constant init model, not a "
+                f"{type(self._init).__name__}"
+            )
+        x = features.float()
+        models, weights, planes, subs = [], [], [], []
+        for ms, wts, sub in zip(self._models, self._weights, self._subspaces):
+            for j, m in enumerate(ms):
+                models.append(m)
+                weights.append(wts[j])
+                planes.append(j)
+                subs.append(sub)
+        out = packed_forest_contrib(
+            x, models, weights, planes, subs, self._dim,
+            cache=self.__dict__.setdefault("_contrib_cache", {}),
+        )
+        out[:, :, -1] += self._init._raw[: self._dim].to(out.device)
+        return out
+
     def raw2probabilityInPlace(self, raw: torch.Tensor) -> torch.Tensor:
         loss = self._loss_obj()
         name = loss.name

@@ -103,6 +103,23 @@ def packed_forest_margin(x, models, weights, subspaces, num_features,
     return _ops.forest_predict(x, trees, w, cache=cache).squeeze(1)
 
 
+def _vote_leaves(m, soft):
+    """Per-node leaf transform of a classification tree under voting
+    (cached on the model): normalized probabilities for soft voting, the
+    one-hot argmax for hard voting."""
+    attr = "_leaf_soft" if soft else "_leaf_hard"
+    lv = getattr(m, attr, None)
+    if lv is None:
+        leaf = m._tree["leaf_value"]
+        if soft:
+            lv = leaf / leaf.sum(dim=1, keepdim=True).clamp_min(1e-12)
+        else:
+            lv = torch.zeros_like(leaf)
+            lv.scatter_(1, leaf.argmax(dim=1, keepdim=True), 1.0)
+        setattr(m, attr, lv)
+    return lv
+
+
 def packed_forest_vote(x, models, subspaces, num_features, soft,
                        cache=None):
     """Bagging-classifier voting as ONE packed forest_predict call.
@@ -118,21 +135,11 @@ def packed_forest_vote(x, models, subspaces, num_features, soft,
     if not models:
         return None
     trees = []
-    attr = "_leaf_soft" if soft else "_leaf_hard"
     for m, sub in zip(models, subspaces):
         if not isinstance(m, DecisionTreeClassificationModel):
             return None
         t = m._tree
-        lv = getattr(m, attr, None)
-        if lv is None:
-            leaf = t["leaf_value"]
-            if soft:
-                lv = leaf / leaf.sum(dim=1, keepdim=True).clamp_min(1e-12)
-            else:
-                k = leaf.shape[1]
-                lv = torch.zeros_like(leaf)
-                lv.scatter_(1, leaf.argmax(dim=1, keepdim=True), 1.0)
-            setattr(m, attr, lv)
+        lv = _vote_leaves(m, soft)
         identity = sub is None or (
             sub.numel() == num_features
             and bool((sub.cpu() == torch.arange(num_features)).all())
@@ -151,6 +158,53 @@ def packed_forest_vote(x, models, subspaces, num_features, soft,
         trees.append(dict(t, feature=feat, leaf_value=lv))
     w = torch.ones(len(trees), dtype=torch.float32)
     return _ops.forest_predict(x, trees, w, cache=cache)
+
+
+def packed_forest_contrib(x, models, weights, planes, subspaces, num_planes,
+                          vote=None, cache=None):
+    """Per-row feature contributions of an ensemble of built-in trees as ONE
+    ``forest_contrib`` call: ``[N, num_planes, F + 1]``, column F the bias
+    (semantics in docs/contributions.md).  Member i adds ``weights[i]``
+    times its tree into plane ``planes[i]`` (a K-vector-leaf tree into
+    planes ``planes[i] .. planes[i] + K - 1``).  Subspaced members are
+    reported in the ORIGINAL feature space through the same
+    ``_tree_orig_feats`` remap the packed predictors use.  ``vote``
+    ("soft" / "hard") swaps in the per-node leaf transform of
+    ``packed_forest_vote`` to explain the vote sums.  Raises
+    ValueError for a member that is not a built-in tree."""
+    from ..models.tree import _TreeModelMixin
+    from ..ops import dispatch as _ops
+
+    num_features = x.shape[1]
+    trees = []
+    for i, (m, sub) in enumerate(zip(models, subspaces)):
+        if not isinstance(m, _TreeModelMixin):
+            raise ValueError(
+                f"predictContrib needs built-in tree members; member {i} is "
+                f"a {type(m).__name__}"
+            )
+        t = m._tree
+        if vote is not None:
+            t = dict(t, leaf_value=_vote_leaves(m, vote == "soft"))
+        identity = sub is None or (
+            sub.numel() == num_features
+            and bool((sub.cpu() == torch.arange(num_features)).all())
+        )
+        if not identity:
+            remapped = getattr(m, "_tree_orig_feats", None)
+            if remapped is None:
+                fl = t["feature"].long()
+                sub_dev = sub.to(fl.device)
+                remapped = torch.where(
+                    fl >= 0, sub_dev[fl.clamp_min(0)], fl
+                ).to(torch.int32)
+                m._tree_orig_feats = remapped
+            t = dict(t, feature=remapped)
+        trees.append(t)
+    return _ops.forest_contrib(
+        x, trees, [float(v) for v in weights], [int(p) for p in planes],
+        num_planes, cache=cache,
+    )
 
 
 def ensemble_feature_importances(models, weights, subspaces, num_features):

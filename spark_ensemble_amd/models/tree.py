@@ -154,6 +154,14 @@ class _TreeModelMixin:
             max_depth=64,
         )
 
+    def _contrib(self, x: torch.Tensor) -> torch.Tensor:
+        """[N, D, F + 1] contributions of the tree's D leaf outputs."""
+        d = self._tree["leaf_value"].shape[1]
+        return ops.forest_contrib(
+            x, [self._tree], None, None, d,
+            cache=self.__dict__.setdefault("_contrib_cache", {}),
+        )
+
     @property
     def depth(self) -> int:
         # derived: longest root-to-leaf path
@@ -268,6 +276,12 @@ class DecisionTreeRegressionModel(_TreeModelMixin, RegressionModel, _TreeParams)
 
     def predict(self, features: torch.Tensor) -> torch.Tensor:
         return self._predict_values(features.float()).squeeze(1)
+
+    def predictContrib(self, features: torch.Tensor) -> torch.Tensor:
+        """Per-row additive feature contributions ``[N, F + 1]`` (path-
+        dependent TreeSHAP, docs/contributions.md): column F is the bias and
+        every row sums to ``predict``.  NaN features are not supported."""
+        return self._contrib(features.float())[:, 0, :]
 
 
 def fit_tree_forest(learner, edges, bins, labels, weights, comm=None,
@@ -504,6 +518,13 @@ class DecisionTreeClassificationModel(
     def predictRaw(self, features: torch.Tensor) -> torch.Tensor:
         # leaf values are class-probability vectors; raw = probabilities
         return self._predict_values(features.float())
+
+    def predictContrib(self, features: torch.Tensor) -> torch.Tensor:
+        """Per-row additive feature contributions ``[N, K, F + 1]``, one
+        plane per class (path-dependent TreeSHAP, docs/contributions.md):
+        column F is the bias and plane k of every row sums to
+        ``predictRaw[:, k]``.  NaN features are not supported."""
+        return self._contrib(features.float())
 
     def raw2probabilityInPlace(self, raw: torch.Tensor) -> torch.Tensor:
         s = raw.sum(dim=1, keepdim=True).clamp_min(1e-12)

@@ -87,7 +87,8 @@ def grow_tree(
     """Grow one tree; returns flat node arrays:
 
     feature [n] int32 (-1 leaf), threshold [n] f32, left_child [n] int32
-    (right = left+1), leaf_value [n, D] f32.
+    (right = left+1), leaf_value [n, D] f32, node_weight [n] f32 (the
+    node's total hessian/weight, its "cover").
 
     ``train_pred_out``: pass a list to ALSO receive the training-row
     predictions [N, D] (appended) — training already partitions every row
@@ -185,6 +186,9 @@ def _grow_tree_seq(
     thrs: List[float] = []
     lefts: List[int] = []
     leaves: List[Optional[torch.Tensor]] = []
+    # per-node cover: the hessian/weight channel of the node's totals row
+    # (the number its leaf mean divides by), kept for forest_contrib
+    covers: List[float] = []
 
     def alloc_nodes(k: int) -> int:
         start = len(feats)
@@ -192,6 +196,7 @@ def _grow_tree_seq(
         thrs.extend([0.0] * k)
         lefts.extend([-1] * k)
         leaves.extend([None] * k)
+        covers.extend([0.0] * k)
         return start
 
     root = alloc_nodes(1)
@@ -216,6 +221,7 @@ def _grow_tree_seq(
     node_ids = [root]
     offsets = torch.tensor([0, row_idx.numel()], dtype=torch.int64)
     totals = root_tot.unsqueeze(0)  # [n_active, C] GLOBAL stats, cpu
+    covers[root] = float(totals[0, D])
     # parent-level histograms (device, GLOBAL sums) for sibling subtraction
     hists: Optional[torch.Tensor] = None
     parent_of: List[int] = []  # active idx -> parent's active idx in prev level
@@ -395,6 +401,7 @@ def _grow_tree_seq(
                 (rcid, le, re, r_stats, l_cnt > r_cnt),
             ):
                 next_nodes.append(cid)
+                covers[cid] = float(st[D])
                 next_off.append(next_off[-1] + (e - s))
                 next_tot_rows.append(st)
                 nb_mask.append(built)
@@ -427,6 +434,7 @@ def _grow_tree_seq(
         "threshold": torch.tensor(thrs, dtype=torch.float32),
         "left_child": torch.tensor(lefts, dtype=torch.int32),
         "leaf_value": leaf_value,
+        "node_weight": torch.tensor(covers, dtype=torch.float32),
         "feature_importance": (fi / fi_tot if fi_tot > 0 else fi).to(
             torch.float32
         ),
@@ -700,6 +708,7 @@ def grow_forest(
     thrs_t = torch.zeros(T, max_nodes, dtype=torch.float32)
     lefts_t = torch.full((T, max_nodes), -1, dtype=torch.int32)
     leaves_t = torch.zeros(T, max_nodes, D, dtype=torch.float32)
+    covers_t = torch.zeros(T, max_nodes, dtype=torch.float32)
     cur_len = torch.ones(T, dtype=torch.long)
     fi = torch.zeros(T, F, dtype=torch.float64)
 
@@ -746,6 +755,11 @@ def grow_forest(
         if comm is not None:
             comm.all_reduce_(root_tot)
         totals = root_tot.cpu()
+
+    # node covers (the hess channel of each node's totals row) are taken
+    # from the host totals unchanged; the root's here, the children's in
+    # the deferred writes of the level that creates them
+    covers_t[:, 0] = totals[:, D]
 
     # active level state (host tensors; sorted by tree by construction)
     node_tree = torch.arange(T, dtype=torch.long)
@@ -917,14 +931,6 @@ def grow_forest(
         cid = cur_len[t_ids] + 2 * rank
         cur_len += 2 * counts
 
-        def _writes(t_ids=t_ids, nids=nids, f_l=f_l, b_l=b_l,
-                    gains=gain_cpu[s_idx].double(), cid=cid):
-            feats_t[t_ids, nids] = f_l.to(torch.int32)
-            thrs_t[t_ids, nids] = edges_cpu[f_l, b_l]
-            fi.index_put_((t_ids, f_l), gains, accumulate=True)
-            lefts_t[t_ids, nids] = cid.to(torch.int32)
-        pending_writes = _writes
-
         hists = hists.index_select(0, _to_dev_async(s_idx, device))
 
         # ----- next level bookkeeping ------------------------------------
@@ -942,6 +948,17 @@ def grow_forest(
                                    dtype=torch.long).repeat_interleave(2)
         node_tree = t_ids.repeat_interleave(2)
         node_nid = torch.stack([cid, cid + 1], dim=1).reshape(-1)
+
+        def _writes(t_ids=t_ids, nids=nids, f_l=f_l, b_l=b_l,
+                    gains=gain_cpu[s_idx].double(), cid=cid,
+                    l_cov=l_st[:, D], r_cov=r_st[:, D]):
+            feats_t[t_ids, nids] = f_l.to(torch.int32)
+            thrs_t[t_ids, nids] = edges_cpu[f_l, b_l]
+            fi.index_put_((t_ids, f_l), gains, accumulate=True)
+            lefts_t[t_ids, nids] = cid.to(torch.int32)
+            covers_t[t_ids, cid] = l_cov
+            covers_t[t_ids, cid + 1] = r_cov
+        pending_writes = _writes
 
         if pr_async is not None:
             new_rows, new_offs, _ = ops.partition_rows_finish(*pr_async)
@@ -976,6 +993,7 @@ def grow_forest(
             "threshold": thrs_t[t, :n_nodes].clone(),
             "left_child": lefts_t[t, :n_nodes].clone(),
             "leaf_value": leaves_t[t, :n_nodes].clone().reshape(n_nodes, D),
+            "node_weight": covers_t[t, :n_nodes].clone(),
             "feature_importance": (
                 fi[t] / fi_tot[t] if float(fi_tot[t]) > 0 else fi[t]
             ).to(torch.float32),

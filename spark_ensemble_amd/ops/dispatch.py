@@ -9,6 +9,7 @@ SEA_ALLOW_EAGER=1 to override for debugging only.
 
 from __future__ import annotations
 
+import math
 import os
 from typing import Optional
 
@@ -699,6 +700,143 @@ def _forest_predict_packed(m, x, pack):
                      pack["lefts"], pack["leaves"], pack["offsets32"],
                      pack["w"], D)
     return out
+
+
+# ---- per-row feature contributions (csrc/tree_contrib.hip) ---------------
+
+CONTRIB_MAX_PATH = 32       # unique features on one path (lane group <= 32)
+CONTRIB_LDS_BYTES = 163840  # the tile's i64 accumulators + f32 x rows
+CONTRIB_MAX_ROWS = 64       # rows per tile once F is small enough
+CONTRIB_MIN_ROWS = 4        # below this a path load is amortised too little
+_CONTRIB_GROUPS = (8, 16, 32)
+
+# what the last forest_contrib call did: {"path": "native" | "reference",
+# "rows_per_tile": R} (tests assert the route without guessing the policy)
+last_forest_contrib_info: dict = {}
+
+
+def contrib_rows_per_tile(num_features: int) -> int:
+    """Rows R of one LDS tile for F features: [R][F] i64 fixed-point
+    accumulators plus [R][F] f32 of x within 160 KiB, capped at
+    CONTRIB_MAX_ROWS.  The native kernel serves F while R >=
+    CONTRIB_MIN_ROWS."""
+    return min(CONTRIB_MAX_ROWS, CONTRIB_LDS_BYTES // (12 * int(num_features)))
+
+
+def _pack_contrib(trees, weights, planes, num_planes, dev):
+    """Path tables of the contribution kernel, built once per (model,
+    device).  Paths are sorted by plane, then lane-group width, then m;
+    ``ranges[p]`` holds plane p's bucket boundaries (8 | 16 | 32 | end)."""
+    tb = reference.contrib_paths(trees, weights, planes, num_planes)
+    pack = {"T": len(trees), "dev": dev, "num_planes": num_planes,
+            "tables": tb, "bias": tb["bias"]}
+    m = tb["m"]
+    m_max = int(m.max()) if m.numel() else 0
+    pack["m_max"] = m_max
+    pack["f_max"] = int(tb["feat"].max()) if tb["feat"].numel() else -1
+    # z <= 0 only comes from a node of zero cover and non-additive covers
+    # only from hand-made dicts; no grower emits either.  The kernel's
+    # factors assume z > 0, its fixed-point range additive covers.
+    pack["native_ok"] = (
+        m_max <= CONTRIB_MAX_PATH and tb["covers_additive"]
+        and (tb["z"].numel() == 0 or bool((tb["z"] > 0).all()))
+        and math.isfinite(tb["bound"]))
+    if not pack["native_ok"]:
+        return pack
+    # power-of-two fixed-point scale: every partial sum of a cell stays
+    # under 2 * bound, which the scale maps to 2^50 (the kernel's integer
+    # conversion holds up to 2^51)
+    pack["scale"] = 1.0
+    if tb["bound"] > 0:
+        pack["scale"] = 2.0 ** max(
+            -1000, min(1000, 49 - math.frexp(tb["bound"])[1]))
+    bucket = torch.bucketize(m, torch.tensor(_CONTRIB_GROUPS), right=False)
+    key = (tb["plane"] * 4 + bucket) * (CONTRIB_MAX_PATH + 1) + m
+    order = torch.argsort(key, stable=True)
+    pb = (tb["plane"] * 4 + bucket)[order]
+    # boundaries: first path of (plane p, bucket >= b) for b = 0..3
+    ranges = torch.searchsorted(
+        pb, torch.arange(num_planes * 4, dtype=torch.int64)
+    ).reshape(num_planes, 4).clone()
+    ends = torch.searchsorted(
+        pb, (torch.arange(num_planes, dtype=torch.int64) + 1) * 4)
+    ranges[:, 3] = ends
+    feat_bits = (
+        tb["feat"]
+        | ((tb["flags"] & reference.CONTRIB_HAS_LO) != 0).long() << 29
+        | ((tb["flags"] & reference.CONTRIB_HAS_HI) != 0).long() << 30
+    )
+
+    def up(t, dtype):
+        return t.to(dtype).contiguous().to(dev)
+
+    pack.update(
+        ranges=up(ranges, torch.int32),
+        path_off=up(tb["off"][order], torch.int32),
+        path_m=up(m[order], torch.int32),
+        path_plane=up(tb["plane"][order], torch.int32),
+        path_v=up(tb["v"][order], torch.float32),
+        e_feat=up(feat_bits, torch.int32),
+        e_lo=up(tb["lo"], torch.float32),
+        e_hi=up(tb["hi"], torch.float32),
+        e_z=up(tb["z"], torch.float32),
+        bias_dev=up(tb["bias"], torch.float32),
+    )
+    return pack
+
+
+def forest_contrib(x, trees, weights=None, planes=None, num_planes=1,
+                   cache=None):
+    """Per-row additive feature contributions (path-dependent TreeSHAP) of
+    a weighted forest: ``[N, num_planes, F + 1]`` f32, column F the bias;
+    tree t adds its output d into plane ``planes[t] + d``.  Semantics:
+    docs/contributions.md and ``reference.forest_contrib``.
+
+    ``cache``: caller-owned dict; the path tables are built once per
+    (model, device) and kept under "contrib_pack".  On the GPU the gfx950
+    kernel computes the feature columns and the bias column (row-
+    independent, summed in float64 on the host) is filled in here.  Forests
+    with a path of more than CONTRIB_MAX_PATH unique features, and feature
+    counts whose row tile falls under CONTRIB_MIN_ROWS, run the torch
+    reference op on the same device.
+    """
+    if x.is_cuda and trees and x.dtype == torch.float32:
+        m = _require_hip("forest_contrib")
+        if m is not None:
+            pack = cache.get("contrib_pack") if cache is not None else None
+            if (pack is None or pack["T"] != len(trees)
+                    or pack["dev"] != x.device
+                    or pack["num_planes"] != num_planes):
+                pack = _pack_contrib(trees, weights, planes, num_planes,
+                                     x.device)
+                if cache is not None:
+                    cache["contrib_pack"] = pack
+            N, F = x.shape
+            if pack["f_max"] >= F:
+                raise ValueError(
+                    f"forest splits on feature {pack['f_max']} but x has "
+                    f"{F} columns"
+                )
+            R = contrib_rows_per_tile(F)
+            if pack["native_ok"] and R >= CONTRIB_MIN_ROWS:
+                out = torch.empty(N, num_planes, F + 1, dtype=torch.float32,
+                                  device=x.device)
+                m.forest_contrib(
+                    out, x.contiguous(), pack["ranges"], pack["path_off"],
+                    pack["path_m"], pack["path_v"], pack["e_feat"],
+                    pack["e_lo"], pack["e_hi"], pack["e_z"], int(R),
+                    pack["scale"],
+                )
+                out[:, :, F] = pack["bias_dev"]
+                last_forest_contrib_info.update(path="native",
+                                                rows_per_tile=R)
+                return out
+            last_forest_contrib_info.update(path="reference",
+                                            rows_per_tile=R)
+            return reference.forest_contrib(
+                x, trees, weights, planes, num_planes, tables=pack["tables"])
+    last_forest_contrib_info.update(path="reference", rows_per_tile=0)
+    return reference.forest_contrib(x, trees, weights, planes, num_planes)
 
 
 def logreg_loss_grad(x, y_int, w, wmat, has_bias):

@@ -388,3 +388,217 @@ def logreg_loss_grad(x, y_int, w, wmat, has_bias):
     gw = x.T @ gmat
     gb = gmat.sum(dim=0) if has_bias else torch.zeros(k, device=x.device)
     return torch.cat([nll.reshape(1), gw.reshape(-1), gb.reshape(-1)])
+
+
+# ---------------------------------------------------------------------------
+# Per-row feature contributions (path-dependent TreeSHAP; semantics in
+# docs/contributions.md)
+# ---------------------------------------------------------------------------
+
+CONTRIB_HAS_LO = 1  # element flag bits
+CONTRIB_HAS_HI = 2
+
+
+def _tree_paths(tree: dict):
+    """Root-to-leaf paths of one tree with repeated features merged.
+
+    Returns ``[(leaf_id, [(feature, lo, has_lo, hi, has_hi, z), ...]), ...]``
+    in left-to-right leaf order: a row satisfies element e iff
+    ``lo < x[feature] <= hi`` (each bound only when its flag is set), and z
+    is the product of child/parent covers over the merged nodes, in float64.
+    """
+    if "node_weight" not in tree:
+        raise ValueError(
+            "tree has no node_weight (per-node covers): it was fitted or "
+            "saved before covers were recorded; refit the model to compute "
+            "contributions"
+        )
+    feat = tree["feature"].cpu().tolist()
+    thr = tree["threshold"].cpu().double().tolist()
+    left = tree["left_child"].cpu().tolist()
+    cov = tree["node_weight"].cpu().double().tolist()
+    paths = []
+    stack = [(0, {})]
+    while stack:
+        nid, el = stack.pop()
+        f = feat[nid]
+        if f < 0:
+            paths.append((nid, [(k,) + v for k, v in el.items()]))
+            continue
+        t, c, l = thr[nid], cov[nid], left[nid]
+        for child, go_left in ((l + 1, False), (l, True)):  # left pops first
+            z = cov[child] / c if c > 0 else 0.0
+            lo, has_lo, hi, has_hi, zz = el.get(f, (0.0, False, 0.0, False, 1.0))
+            if go_left:
+                hi, has_hi = (min(hi, t) if has_hi else t), True
+            else:
+                lo, has_lo = (max(lo, t) if has_lo else t), True
+            e = dict(el)
+            e[f] = (lo, has_lo, hi, has_hi, zz * z)
+            stack.append((child, e))
+    return paths
+
+
+def contrib_paths(trees: List[dict], weights=None, planes=None,
+                  num_planes: int = 1) -> dict:
+    """Flat host tables of every path of a weighted forest (float64 values),
+    shared by :func:`forest_contrib` and the GPU packer.
+
+    Per path: ``off`` (first element), ``m`` (unique elements), ``plane``,
+    ``v`` (leaf value x tree weight).  Per element: ``feat``, ``lo``, ``hi``,
+    ``flags`` (CONTRIB_HAS_LO | CONTRIB_HAS_HI), ``z``.  ``bias`` [num_planes]
+    is ``sum_leaves v * c_leaf / c_root``; ``bound`` is
+    ``sum_t |w_t| max|leaf_t|`` (no cell of the result, and no partial sum of
+    its path terms, exceeds twice that when ``covers_additive``: every
+    parent's cover equals the sum of its children's to 1e-3 relative, as the
+    growers' do).  A tree with D leaf outputs adds
+    output d into plane ``planes[t] + d``; its paths are listed once per
+    output with a nonzero leaf value and share their elements.  Trees of
+    weight 0 and paths of value 0 are left out (they add exactly nothing).
+    """
+    T = len(trees)
+    w_l = [1.0] * T if weights is None else [float(v) for v in weights]
+    p_l = [0] * T if planes is None else [int(v) for v in planes]
+    assert len(w_l) == T and len(p_l) == T
+    p_off, p_m, p_plane, p_v = [], [], [], []
+    e_feat, e_lo, e_hi, e_flags, e_z = [], [], [], [], []
+    bias = [0.0] * num_planes
+    bound, additive = 0.0, True
+    for tree, w, pl in zip(trees, w_l, p_l):
+        leaf = tree["leaf_value"].cpu().double()
+        D = leaf.shape[1]
+        if pl < 0 or pl + D > num_planes:
+            raise ValueError(
+                f"tree with {D} outputs at plane {pl} exceeds num_planes="
+                f"{num_planes}"
+            )
+        paths = _tree_paths(tree)  # validates node_weight even at weight 0
+        if w == 0.0:
+            continue
+        bound += abs(w) * float(leaf.abs().max())
+        cov_t = tree["node_weight"].cpu().double()
+        split = (tree["feature"].cpu() >= 0).nonzero(as_tuple=True)[0]
+        kids = tree["left_child"].cpu().long()[split]
+        additive = additive and bool(
+            ((cov_t[kids] + cov_t[kids + 1] - cov_t[split]).abs()
+             <= 1e-3 * cov_t[split]).all())
+        leaf = leaf.tolist()
+        cov = cov_t.tolist()
+        for leaf_id, elems in paths:
+            off = len(e_feat)
+            listed = False
+            for d in range(D):
+                v = leaf[leaf_id][d] * w
+                if v == 0.0:
+                    continue
+                if cov[0] > 0:
+                    bias[pl + d] += v * cov[leaf_id] / cov[0]
+                if not elems:
+                    continue
+                if not listed:
+                    for f, lo, has_lo, hi, has_hi, z in elems:
+                        e_feat.append(f)
+                        e_lo.append(lo)
+                        e_hi.append(hi)
+                        e_flags.append((CONTRIB_HAS_LO if has_lo else 0)
+                                       | (CONTRIB_HAS_HI if has_hi else 0))
+                        e_z.append(z)
+                    listed = True
+                p_off.append(off)
+                p_m.append(len(elems))
+                p_plane.append(pl + d)
+                p_v.append(v)
+    i64, f64 = torch.int64, torch.float64
+    return {
+        "off": torch.tensor(p_off, dtype=i64),
+        "m": torch.tensor(p_m, dtype=i64),
+        "plane": torch.tensor(p_plane, dtype=i64),
+        "v": torch.tensor(p_v, dtype=f64),
+        "feat": torch.tensor(e_feat, dtype=i64),
+        "lo": torch.tensor(e_lo, dtype=f64),
+        "hi": torch.tensor(e_hi, dtype=f64),
+        "flags": torch.tensor(e_flags, dtype=i64),
+        "z": torch.tensor(e_z, dtype=f64),
+        "bias": torch.tensor(bias, dtype=f64),
+        "bound": bound,
+        "covers_additive": additive,
+    }
+
+
+def gauss_legendre_01(n: int):
+    """Nodes and weights (float64 tensors) of the n-point Gauss-Legendre
+    rule on [0, 1]; exact for polynomials of degree <= 2n - 1."""
+    import numpy as np
+
+    xs, ws = np.polynomial.legendre.leggauss(n)
+    return torch.from_numpy((xs + 1.0) / 2.0), torch.from_numpy(ws / 2.0)
+
+
+def forest_contrib(
+    x: torch.Tensor,  # [N, F] f32 or f64
+    trees: List[dict],
+    weights=None,
+    planes=None,
+    num_planes: int = 1,
+    tables: Optional[dict] = None,
+) -> torch.Tensor:
+    """Per-row additive feature contributions: ``[N, num_planes, F + 1]`` in
+    the dtype of ``x`` (float64 in, float64 throughout); column F is the
+    bias.  Rows sum to the weighted forest prediction of the plane.
+
+    Evaluates the path form: for a path with m unique elements the
+    coefficient sum ``sum_k k!(m-1-k)!/m! [t^k] prod_{j != e}(z_j + o_j t)``
+    equals ``integral_0^1 prod_{j != e}(z_j (1 - s) + o_j s) ds``, and the
+    integrand has degree m - 1, so Gauss-Legendre with ceil(m / 2) nodes is
+    exact.  The product over the other elements is prefix x suffix: nothing
+    is divided out and every term is non-negative.  Vectorised over rows and
+    over all paths of equal m.  ``tables`` takes a precomputed
+    :func:`contrib_paths` result.
+    """
+    assert x.dim() == 2
+    dt = x.dtype if x.dtype == torch.float64 else torch.float32
+    x = x.to(dt)
+    N, F = x.shape
+    dev = x.device
+    tb = tables if tables is not None else contrib_paths(
+        trees, weights, planes, num_planes)
+    out = torch.zeros(N, num_planes, F + 1, dtype=dt, device=dev)
+    out[:, :, F] = tb["bias"].to(device=dev, dtype=dt)
+    if tb["feat"].numel() and int(tb["feat"].max()) >= F:
+        raise ValueError(
+            f"forest splits on feature {int(tb['feat'].max())} but x has "
+            f"{F} columns"
+        )
+    flat = out.view(N, num_planes * (F + 1))
+    for m in sorted(set(tb["m"].tolist())):
+        sel = (tb["m"] == m).nonzero(as_tuple=True)[0]
+        q = (m + 1) // 2
+        s64, w64 = gauss_legendre_01(q)
+        s = s64.to(device=dev, dtype=dt)
+        a = (1.0 - s64).to(device=dev, dtype=dt)
+        wq = w64.to(device=dev, dtype=dt)
+        # chunk so the [N, P, m, q] factor tensor stays modest
+        step = max(1, (1 << 22) // max(N * m * q, 1))
+        for c0 in range(0, sel.numel(), step):
+            ps = sel[c0:c0 + step]
+            eidx = tb["off"][ps].unsqueeze(1) + torch.arange(m)  # [P, m]
+            feat = tb["feat"][eidx].to(dev)
+            flags = tb["flags"][eidx].to(dev)
+            lo = tb["lo"][eidx].to(device=dev, dtype=dt)
+            hi = tb["hi"][eidx].to(device=dev, dtype=dt)
+            z = tb["z"][eidx].to(device=dev, dtype=dt)
+            v = tb["v"][ps].to(device=dev, dtype=dt)
+            xv = x[:, feat.reshape(-1)].reshape(N, -1, m)
+            o = (((flags & CONTRIB_HAS_LO) == 0) | (xv > lo)) & (
+                ((flags & CONTRIB_HAS_HI) == 0) | (xv <= hi))
+            o = o.to(dt)  # [N, P, m]
+            f = (z.unsqueeze(-1) * a).unsqueeze(0) + o.unsqueeze(-1) * s
+            one = torch.ones_like(f[:, :, :1])
+            pre = torch.cat([one, f[:, :, :-1].cumprod(dim=2)], dim=2)
+            suf = torch.cat(
+                [f[:, :, 1:].flip(2).cumprod(dim=2).flip(2), one], dim=2)
+            S = ((pre * suf) * wq).sum(dim=-1)  # [N, P, m]
+            contrib = v.view(1, -1, 1) * (o - z) * S
+            col = tb["plane"][ps].to(dev).unsqueeze(1) * (F + 1) + feat
+            flat.index_add_(1, col.reshape(-1), contrib.reshape(N, -1))
+    return out

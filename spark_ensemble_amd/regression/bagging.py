@@ -258,6 +258,21 @@ class BaggingRegressionModel(RegressionModel, _BaggingRegressorParams):
             acc = p if acc is None else acc + p
         return acc / mcount
 
+    def predictContrib(self, features: torch.Tensor) -> torch.Tensor:
+        """Per-row additive feature contributions ``[N, F + 1]`` in the
+        original feature space (path-dependent TreeSHAP,
+        docs/contributions.md): column F is the bias and every row sums to
+        ``predict``.  Raises ValueError for a member that is not a built-in
+        tree.  NaN features are not supported."""
+        from ..ensemble.utils import packed_forest_contrib
+
+        mcount = len(self._models)
+        return packed_forest_contrib(
+            features.float(), self._models, [1.0 / mcount] * mcount,
+            [0] * mcount, self._subspaces, 1,
+            cache=self.__dict__.setdefault("_contrib_cache", {}),
+        )[:, 0, :]
+
     def _save_impl(self, path: str):
         persistence.save_metadata(
             self, path,

@@ -472,6 +472,39 @@ class GBMRegressionModel(RegressionModel, _GBMRegressorParams):
             out = out + wgt * m.predict(slice_features(x, sub))
         return out
 
+    def predictContrib(self, features: torch.Tensor) -> torch.Tensor:
+        """Per-row additive feature contributions ``[N, F + 1]`` (path-
+        dependent TreeSHAP, docs/contributions.md): column F is the bias and
+        every row sums to ``predict``.  A constant init goes into the bias;
+        an init that is a tree model joins the forest with weight 1; any
+        other init, or a stage that is not a built-in tree, raises
+        ValueError.  NaN features are not supported."""
+        from ..ensemble.utils import packed_forest_contrib
+        from ..models.dummy import DummyRegressionModel
+        from ..models.tree import DecisionTreeRegressionModel
+
+        x = features.float()
+        models, weights = list(self._models), list(self._weights)
+        subs = list(self._subspaces)
+        const = 0.0
+        if isinstance(self._init, DummyRegressionModel):
+            const = float(self._init._constant)
+        elif isinstance(self._init, DecisionTreeRegressionModel):
+            models.insert(0, self._init)
+            weights.insert(0, 1.0)
+            subs.insert(0, None)
+        else:
+            raise ValueError(
+                "predictContrib needs a constant or tree init model, not a "
+                f"{type(self._init).__name__}"
+            )
+        out = packed_forest_contrib(
+            x, models, weights, [0] * len(models), subs, 1,
+            cache=self.__dict__.setdefault("_contrib_cache", {}),
+        )[:, 0, :]
+        out[:, -1] += const
+        return out
+
     @property
     def numModels(self) -> int:
         return len(self._models)

@@ -21,6 +21,7 @@ SRC = [
     os.path.join(REPO, "csrc", "ops.hip"),
     os.path.join(REPO, "csrc", "linear.hip"),
     os.path.join(REPO, "csrc", "wide_class.hip"),
+    os.path.join(REPO, "csrc", "tree_contrib.hip"),
 ]
 OUT = os.path.join(REPO, "spark_ensemble_amd", "_hip_ops.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
