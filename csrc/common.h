@@ -37,6 +37,7 @@ enum UploadSlot : int {
   kSlotLeafVal = 7,         // leaf_scatter: leaf values
   kSlotClassChunks = 8,     // hist_build_class: scale + chunk table
   kSlotClassNodes = 9,      // hist_build_class: slot -> node + scales
+  kSlotLevelTable = 10,     // level_split: per-node source rows
   kUploadSlots = 12,
 };
 

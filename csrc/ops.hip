@@ -845,14 +845,17 @@ __global__ void partition_kernel(
   }
 }
 
-void partition_rows(torch::Tensor new_rows, torch::Tensor left_counts,
-                    torch::Tensor bins, torch::Tensor bins_t,
-                    torch::Tensor row_idx,
-                    torch::Tensor node_offsets, torch::Tensor feat,
-                    torch::Tensor thr) {
+// Queues the partition of every node and returns the device cursor table
+// [n_nodes, 2] = {lcur, rcur}: once the kernel has run, lcur - offs[node] is
+// the node's left count.
+static torch::Tensor partition_launch(torch::Tensor new_rows,
+                                      torch::Tensor bins, torch::Tensor bins_t,
+                                      torch::Tensor row_idx,
+                                      torch::Tensor node_offsets,
+                                      torch::Tensor feat, torch::Tensor thr) {
   auto tpA = std::chrono::steady_clock::now();
   CHECK_GPU(new_rows); CHECK_GPU(bins); CHECK_GPU(row_idx);
-  CHECK_GPU(feat); CHECK_GPU(thr); CHECK_GPU(left_counts);
+  CHECK_GPU(feat); CHECK_GPU(thr);
   const int F = (int)bins.size(1);
   const int n_nodes = (int)node_offsets.numel() - 1;
   auto offs = node_offsets.accessor<int64_t, 1>();
@@ -908,7 +911,20 @@ void partition_rows(torch::Tensor new_rows, torch::Tensor left_counts,
               (long)us(tp2, tp3));
     }
   }
-  auto lcur = cursors.view({n_nodes, 2}).select(1, 0);
+  return cursors.view({n_nodes, 2});
+}
+
+void partition_rows(torch::Tensor new_rows, torch::Tensor left_counts,
+                    torch::Tensor bins, torch::Tensor bins_t,
+                    torch::Tensor row_idx,
+                    torch::Tensor node_offsets, torch::Tensor feat,
+                    torch::Tensor thr) {
+  CHECK_GPU(left_counts);
+  auto cursors = partition_launch(new_rows, bins, bins_t, row_idx,
+                                  node_offsets, feat, thr);
+  const int n_nodes = (int)node_offsets.numel() - 1;
+  auto offs = node_offsets.accessor<int64_t, 1>();
+  auto lcur = cursors.select(1, 0);
   // NOTE: this upload was a pageable .to(device) — a SYNCHRONOUS copy that
   // stalled the host ~1 ms/level behind the queued hist/split kernels
   // (found via SEA_PART_DEBUG bracketing); pinned async staging fixes it
@@ -918,6 +934,27 @@ void partition_rows(torch::Tensor new_rows, torch::Tensor left_counts,
                          bins.device());
   auto seg_start = seg_b.view(torch::kInt32);
   left_counts.copy_(lcur - seg_start);
+}
+
+// partition_rows without the device bookkeeping: feat / thr are the int32
+// device tensors of level_split, and the cursor table itself is returned for
+// the caller to copy to the host, where left = lcur - segment start.
+torch::Tensor partition_rows_cursors(torch::Tensor new_rows,
+                                     torch::Tensor bins, torch::Tensor bins_t,
+                                     torch::Tensor row_idx,
+                                     torch::Tensor node_offsets,
+                                     torch::Tensor feat, torch::Tensor thr) {
+  CHECK_CONTIG(new_rows); CHECK_CONTIG(row_idx); CHECK_CONTIG(feat);
+  CHECK_CONTIG(thr);
+  const int64_t n_nodes = node_offsets.numel() - 1;
+  TORCH_CHECK(feat.scalar_type() == torch::kInt32 &&
+                  thr.scalar_type() == torch::kInt32 &&
+                  feat.numel() == n_nodes && thr.numel() == n_nodes,
+              "partition_rows_cursors: feat and thr are int32 [n_nodes]");
+  TORCH_CHECK(new_rows.numel() == row_idx.numel(),
+              "partition_rows_cursors: new_rows must match row_idx");
+  return partition_launch(new_rows, bins, bins_t, row_idx, node_offsets, feat,
+                          thr);
 }
 
 // ---------------------------------------------------------------------------
@@ -1801,36 +1838,16 @@ void line_search_eval(torch::Tensor payload, torch::Tensor label,
 //   a per-node cell — no [n,F,B,C] cumsum/gain tensors ever touch HBM.
 // ---------------------------------------------------------------------------
 
+// The scan of one wave over the B bins of one (node, feature) slice, shared
+// by split_argmax_kernel and level_scan_kernel: loc holds the lane's BPL
+// bins, tot their per-channel sums.
 template <int C>
-__global__ void split_argmax_kernel(
-    unsigned long long* __restrict__ best,  // [n_nodes] pre-zeroed
-    const float* __restrict__ hist,         // [n_nodes, F, B, C]
-    int F, int B, int D, float lam, float min_child_weight,
-    float min_instances) {
-  const int node = blockIdx.x;
-  const int f = blockIdx.y * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (f >= F) return;
-  const float* h = hist + (((int64_t)node * F + f) * (int64_t)B) * C;
+__device__ __forceinline__ void split_scan_wave(
+    unsigned long long* __restrict__ best, float (&loc)[4][C], float (&tot)[C],
+    int node, int f, int lane, int B, int D, float lam,
+    float min_child_weight, float min_instances) {
   const int BPL = (B + 63) >> 6;  // <= 4 for B <= 256
   const int idx_c = C - 1;        // count channel
-
-  float loc[4][C];
-  float tot[C];
-#pragma unroll
-  for (int c = 0; c < C; ++c) tot[c] = 0.0f;
-  for (int i = 0; i < BPL; ++i) {
-    const int b = lane * BPL + i;
-#pragma unroll
-    for (int c = 0; c < C; ++c) loc[i][c] = 0.0f;
-    if (b < B) {
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        loc[i][c] = h[(int64_t)b * C + c];
-        tot[c] += loc[i][c];
-      }
-    }
-  }
   // wave-wide exclusive prefix + parent totals (shfl scan per channel)
   float pre[C], parent[C];
 #pragma unroll
@@ -1893,6 +1910,96 @@ __global__ void split_argmax_kernel(
 }
 
 template <int C>
+__global__ void split_argmax_kernel(
+    unsigned long long* __restrict__ best,  // [n_nodes] pre-zeroed
+    const float* __restrict__ hist,         // [n_nodes, F, B, C]
+    int F, int B, int D, float lam, float min_child_weight,
+    float min_instances) {
+  const int node = blockIdx.x;
+  const int f = blockIdx.y * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (f >= F) return;
+  const float* h = hist + (((int64_t)node * F + f) * (int64_t)B) * C;
+  const int BPL = (B + 63) >> 6;  // <= 4 for B <= 256
+
+  float loc[4][C];
+  float tot[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) tot[c] = 0.0f;
+  for (int i = 0; i < BPL; ++i) {
+    const int b = lane * BPL + i;
+#pragma unroll
+    for (int c = 0; c < C; ++c) loc[i][c] = 0.0f;
+    if (b < B) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        loc[i][c] = h[(int64_t)b * C + c];
+        tot[c] += loc[i][c];
+      }
+    }
+  }
+  split_scan_wave<C>(best, loc, tot, node, f, lane, B, D, lam,
+                     min_child_weight, min_instances);
+}
+
+// split_argmax_kernel for one tree level that reads its sources in place.
+// tab[node] = (built_row, parent_row, sibling_built_row): a built node
+// (built_row >= 0) scans built[built_row]; a derived node scans
+// parent[parent_row] - built[sibling_built_row], subtracted here in f32.
+// Every wave stores the slice it scanned into level[node], which is the next
+// level's ``parent``; at the root level IS built (store == 0) and nothing is
+// copied, so built and level carry no __restrict__.
+template <int C>
+__global__ void level_scan_kernel(
+    unsigned long long* __restrict__ best,  // [n_nodes] pre-zeroed
+    float* level,                           // [n_nodes, F, B, C]
+    const float* built,                     // [n_built, F, B, C]
+    const float* __restrict__ parent,       // [n_prev, F, B, C]
+    const int* __restrict__ tab,            // [n_nodes, 3]
+    int store, int F, int B, int D, float lam, float min_child_weight,
+    float min_instances) {
+  const int node = blockIdx.x;
+  const int f = blockIdx.y * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (f >= F) return;
+  const int b_row = tab[node * 3 + 0];
+  const int64_t slice = (int64_t)B * C;
+  const float* h = built + ((int64_t)(b_row >= 0 ? b_row : tab[node * 3 + 2]) *
+                                F + f) * slice;
+  const float* ph =
+      b_row >= 0 ? nullptr
+                 : parent + ((int64_t)tab[node * 3 + 1] * F + f) * slice;
+  float* o = level + ((int64_t)node * F + f) * slice;
+  const int BPL = (B + 63) >> 6;  // <= 4 for B <= 256
+
+  float loc[4][C];
+  float tot[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) tot[c] = 0.0f;
+  for (int i = 0; i < BPL; ++i) {
+    const int b = lane * BPL + i;
+#pragma unroll
+    for (int c = 0; c < C; ++c) loc[i][c] = 0.0f;
+    if (b < B) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        float v = h[(int64_t)b * C + c];
+        if (ph) v = ph[(int64_t)b * C + c] - v;
+        if (store) o[(int64_t)b * C + c] = v;
+        loc[i][c] = v;
+        tot[c] += loc[i][c];
+      }
+    }
+  }
+  split_scan_wave<C>(best, loc, tot, node, f, lane, B, D, lam,
+                     min_child_weight, min_instances);
+}
+
+// PACK: the level_split outputs.  ``gain`` is then the [n * (3 + C)] f32
+// buffer (gain[n], feat[n], bin[n], left_stats[n, C]) that goes to the host
+// in one copy, left_stats points into it, and feat / bin are the int32
+// tensors the partition kernel reads.
+template <int C, bool PACK = false>
 __global__ void split_decode_kernel(
     float* __restrict__ gain, int* __restrict__ feat, int* __restrict__ bin,
     float* __restrict__ left_stats,  // [n, C]
@@ -1909,6 +2016,10 @@ __global__ void split_decode_kernel(
       gain[node] = -INFINITY;
       feat[node] = -1;
       bin[node] = -1;
+      if (PACK) {
+        gain[gridDim.x + node] = -1.0f;
+        gain[2 * gridDim.x + node] = -1.0f;
+      }
     }
     if (threadIdx.x < C) left_stats[node * C + threadIdx.x] = 0.0f;
     return;
@@ -1930,6 +2041,10 @@ __global__ void split_decode_kernel(
     gain[node] = g;
     feat[node] = f;
     bin[node] = b;
+    if (PACK) {
+      gain[gridDim.x + node] = (float)f;
+      gain[2 * gridDim.x + node] = (float)b;
+    }
   }
   if (threadIdx.x < C) left_stats[node * C + threadIdx.x] = acc[threadIdx.x];
 }
@@ -1981,6 +2096,143 @@ void split_argmax(torch::Tensor gain, torch::Tensor feat, torch::Tensor bin,
     case 8: SA_LAUNCH(8); break;
   }
 #undef SA_LAUNCH
+}
+
+// level_split: the split search of one tree level on its sources in place
+// (level_scan_kernel above).  ``table`` is a host int32 [n, 3] of
+// (built_row, parent_row, sibling_built_row) per active node; siblings are
+// neighbours (j ^ 1), as the grower lays them out.  ``level`` receives the
+// level's full histograms; at the root it may be ``built`` itself.  ``pack``
+// is the f32 [n * (3 + C)] host-bound result, feat / bin the int32 device
+// copies for the partition kernel.  Every row the kernels will touch is
+// checked here, before anything is queued.
+void level_split(torch::Tensor level, torch::Tensor pack, torch::Tensor feat,
+                 torch::Tensor bin, torch::Tensor built, torch::Tensor parent,
+                 torch::Tensor table, int64_t d_dims, double lam,
+                 double min_child_weight, double min_instances,
+                 double min_info_gain) {
+  CHECK_GPU(level); CHECK_GPU(pack); CHECK_GPU(feat); CHECK_GPU(bin);
+  CHECK_GPU(built);
+  CHECK_CONTIG(level); CHECK_CONTIG(pack); CHECK_CONTIG(feat);
+  CHECK_CONTIG(bin); CHECK_CONTIG(built); CHECK_CONTIG(parent);
+  CHECK_CONTIG(table);
+  TORCH_CHECK(!table.is_cuda() && table.scalar_type() == torch::kInt32 &&
+                  table.dim() == 2 && table.size(1) == 3,
+              "level_split: table must be a host int32 [n, 3]");
+  TORCH_CHECK(level.dim() == 4 && built.dim() == 4,
+              "level_split: level and built must be [n, F, B, C]");
+  TORCH_CHECK(level.scalar_type() == torch::kFloat32 &&
+                  built.scalar_type() == torch::kFloat32 &&
+                  pack.scalar_type() == torch::kFloat32 &&
+                  feat.scalar_type() == torch::kInt32 &&
+                  bin.scalar_type() == torch::kInt32,
+              "level_split: f32 histograms and pack, int32 feat and bin");
+  const int64_t n = level.size(0);
+  const int64_t n_built = built.size(0);
+  const int F = (int)level.size(1);
+  const int B = (int)level.size(2);
+  const int C = (int)level.size(3);
+  const int D = d_dims > 0 ? (int)d_dims : C - 2;
+  TORCH_CHECK(built.size(1) == F && built.size(2) == B && built.size(3) == C,
+              "level_split: built and level disagree in F, B, C");
+  const bool has_parent = parent.numel() > 0;
+  int64_t n_prev = 0;
+  if (has_parent) {
+    CHECK_GPU(parent);
+    TORCH_CHECK(parent.dim() == 4 && parent.scalar_type() == torch::kFloat32 &&
+                    parent.size(1) == F && parent.size(2) == B &&
+                    parent.size(3) == C,
+                "level_split: parent and level disagree in F, B, C");
+    n_prev = parent.size(0);
+    TORCH_CHECK(parent.data_ptr() != level.data_ptr(),
+                "level_split: level must not be parent");
+  }
+  TORCH_CHECK(level.device() == built.device() &&
+                  pack.device() == built.device() &&
+                  feat.device() == built.device() &&
+                  bin.device() == built.device() &&
+                  (!has_parent || parent.device() == built.device()),
+              "level_split: all device tensors on one device");
+  TORCH_CHECK(n < ((int64_t)1 << 31), "level_split: too many nodes");
+  TORCH_CHECK(C >= 2 && C <= 8, "level_split: 2 <= C <= 8");
+  TORCH_CHECK(B >= 2 && B <= 256, "level_split: 2 <= B <= 256");
+  TORCH_CHECK(D >= 1 && D < C, "level_split: bad D");
+  TORCH_CHECK(table.size(0) == n, "level_split: one table row per node");
+  TORCH_CHECK(pack.numel() == n * (3 + C) && feat.numel() == n &&
+                  bin.numel() == n,
+              "level_split: pack is [n * (3 + C)], feat and bin are [n]");
+  const bool alias = level.data_ptr() == built.data_ptr();
+  TORCH_CHECK(!alias || n == n_built,
+              "level_split: level may alias built only when every node is "
+              "built in place");
+  auto overlaps = [](const torch::Tensor& a, const torch::Tensor& b) {
+    const char* a0 = (const char*)a.data_ptr();
+    const char* b0 = (const char*)b.data_ptr();
+    return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
+  };
+  TORCH_CHECK(alias || !overlaps(level, built),
+              "level_split: level overlaps built without being it");
+  TORCH_CHECK(!has_parent || !overlaps(level, parent),
+              "level_split: level overlaps parent");
+  auto tb = table.accessor<int, 2>();
+  for (int64_t j = 0; j < n; ++j) {
+    const int br = tb[j][0];
+    if (br >= 0) {
+      TORCH_CHECK(br < n_built, "level_split: built_row ", br, " of node ", j,
+                  " out of range");
+      TORCH_CHECK(!alias || br == j,
+                  "level_split: level aliases built but node ", j,
+                  " is built in row ", br);
+      continue;
+    }
+    TORCH_CHECK(br == -1, "level_split: built_row of node ", j, " is ", br);
+    TORCH_CHECK(!alias, "level_split: level aliases built but node ", j,
+                " is derived");
+    TORCH_CHECK(tb[j][1] >= 0 && tb[j][1] < n_prev,
+                "level_split: parent_row ", tb[j][1], " of node ", j,
+                " out of range");
+    TORCH_CHECK(tb[j][2] >= 0 && tb[j][2] < n_built,
+                "level_split: sibling_built_row ", tb[j][2], " of node ", j,
+                " out of range");
+    const int64_t sib = j ^ 1;
+    TORCH_CHECK(sib < n && tb[sib][0] == tb[j][2],
+                "level_split: the sibling of derived node ", j,
+                " is not the built node in row ", tb[j][2]);
+  }
+  if (n == 0 || F == 0) return;
+  auto tab = h2d_async(table.data_ptr(), (size_t)n * 12, kSlotLevelTable,
+                       level.device());
+  auto best = torch::zeros({n}, level.options().dtype(torch::kInt64));
+  auto stream = at::hip::getCurrentHIPStream();
+  const int fpb = 4;  // features (waves) per block
+  float* pk = pack.data_ptr<float>();
+#define LS_LAUNCH(CC)                                                         \
+  do {                                                                        \
+    hipLaunchKernelGGL(level_scan_kernel<CC>,                                 \
+                       dim3((unsigned)n, (F + fpb - 1) / fpb),                \
+                       dim3(64 * fpb), 0, stream,                             \
+                       (unsigned long long*)best.data_ptr<int64_t>(),         \
+                       level.data_ptr<float>(), built.data_ptr<float>(),      \
+                       has_parent ? parent.data_ptr<float>() : nullptr,       \
+                       (const int*)tab.data_ptr(), alias ? 0 : 1, F, B, D,    \
+                       (float)lam, (float)min_child_weight,                   \
+                       (float)min_instances);                                 \
+    hipLaunchKernelGGL((split_decode_kernel<CC, true>), dim3((unsigned)n),    \
+                       dim3(64), 0, stream, pk, feat.data_ptr<int>(),         \
+                       bin.data_ptr<int>(), pk + 3 * n,                       \
+                       (unsigned long long*)best.data_ptr<int64_t>(),         \
+                       level.data_ptr<float>(), F, B, (float)min_info_gain);  \
+  } while (0)
+  switch (C) {
+    case 2: LS_LAUNCH(2); break;
+    case 3: LS_LAUNCH(3); break;
+    case 4: LS_LAUNCH(4); break;
+    case 5: LS_LAUNCH(5); break;
+    case 6: LS_LAUNCH(6); break;
+    case 7: LS_LAUNCH(7); break;
+    case 8: LS_LAUNCH(8); break;
+  }
+#undef LS_LAUNCH
 }
 
 // csrc/hist_plan.h on host tensors, for tests: touches no device
@@ -2043,6 +2295,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hist_build_class", &hist_build_class,
         "label-indexed node histograms for K-class gini trees");
   m.def("partition_rows", &partition_rows, "block-aggregated node partition");
+  m.def("partition_rows_cursors", &partition_rows_cursors,
+        "node partition that returns its cursor table");
+  m.def("level_split", &level_split,
+        "split search of one tree level on built / parent - sibling in place");
   m.def("tree_predict", &tree_predict, "single-tree batched predict");
   m.def("forest_predict", &forest_predict, "packed-forest weighted predict");
   m.def("forest_predict2", &forest_predict2,

@@ -789,6 +789,18 @@ def grow_forest(
     # Python (measured ~110 us of idle per level without this)
     pending_writes = None
 
+    # fused level path (profiles/level_fused.md): one native split op that
+    # reads built / parent - sibling in place and keeps the level tensor
+    # uncompacted; the partition takes its int32 feat / bin as they are.
+    # Feature masks, the wide class kernel, the feature-chunk pipelined
+    # reduce and CPU tensors keep the composed ops.
+    fused = (
+        bins.is_cuda and C <= 8 and feature_masks is None
+        and not (comm is not None and comm.is_distributed and F >= 32)
+        and ops.level_fused_enabled()
+    )
+    parent_row_t: Optional[torch.Tensor] = None  # cpu long: row in ``hists``
+
     def _finalize_and_capture(idx_t, offs, ridx):
         if idx_t.numel() == 0:
             return
@@ -837,11 +849,20 @@ def grow_forest(
                 new_h = ops.hist_build_forest(
                     bins, gh, row_idx, offsets,
                     (node_tree * C).to(torch.int32), B, C, gh_max, d_dims=D,
+                    identity_rows=(fused and root_rows is None and T == 1),
                 )
-            hists, gain, feat, b, left_stats = _finish_level_split(
-                new_h, None, None, None, None, None, n_active, (F, B, C),
-                device, comm, split_args, split_mask=lvl_mask,
-            )
+            if fused:
+                if comm is not None:
+                    comm.all_reduce_(new_h)
+                table = torch.full((n_active, 3), -1, dtype=torch.int32)
+                table[:, 0] = torch.arange(n_active, dtype=torch.int32)
+                hists, pack_d, feat, b = ops.level_split(
+                    new_h, None, table, **split_args)
+            else:
+                hists, gain, feat, b, left_stats = _finish_level_split(
+                    new_h, None, None, None, None, None, n_active, (F, B, C),
+                    device, comm, split_args, split_mask=lvl_mask,
+                )
         else:
             built_cpu = built_mask_t.nonzero(as_tuple=True)[0]
             nb_cpu = (~built_mask_t).nonzero(as_tuple=True)[0]
@@ -868,22 +889,38 @@ def grow_forest(
                         torch.zeros(built_cpu.numel(), dtype=torch.int32),
                         B, C, gh_max, d_dims=D, gh_by_position=True,
                     )
-            hists, gain, feat, b, left_stats = _finish_level_split(
-                bh, _to_dev_async(built_cpu, device), hists,
-                _to_dev_async(nb_cpu, device),
-                _to_dev_async(nb_cpu ^ 1, device),
-                _to_dev_async(parent_of_t[nb_cpu], device), n_active,
-                (F, B, C), device, comm, split_args, split_mask=lvl_mask,
-            )
+            if fused:
+                if comm is not None:
+                    comm.all_reduce_(bh)
+                # per node: its row in ``bh``, or its parent's row in the
+                # kept (uncompacted) previous level and its sibling's row
+                # in ``bh`` — one small table, uploaded by the op
+                brow = torch.full((n_active,), -1, dtype=torch.long)
+                brow[built_cpu] = torch.arange(built_cpu.numel())
+                table = torch.full((n_active, 3), -1, dtype=torch.int32)
+                table[:, 0] = brow
+                table[nb_cpu, 1] = parent_row_t[nb_cpu].to(torch.int32)
+                table[nb_cpu, 2] = brow[nb_cpu ^ 1].to(torch.int32)
+                hists, pack_d, feat, b = ops.level_split(
+                    bh, hists, table, **split_args)
+            else:
+                hists, gain, feat, b, left_stats = _finish_level_split(
+                    bh, _to_dev_async(built_cpu, device), hists,
+                    _to_dev_async(nb_cpu, device),
+                    _to_dev_async(nb_cpu ^ 1, device),
+                    _to_dev_async(parent_of_t[nb_cpu], device), n_active,
+                    (F, B, C), device, comm, split_args, split_mask=lvl_mask,
+                )
         # ONE D2H for the level's split results (gain / feat / bin ids
         # are exact in f32 — F < 2^24, B <= 256), queued BEFORE the
         # partition kernel and awaited via an event: the host reads the
         # split outcome the moment split_argmax finishes and does all its
         # bookkeeping WHILE the partition kernel still runs
-        pack_d = torch.cat([
-            gain, feat.to(torch.float32), b.to(torch.float32),
-            left_stats.reshape(-1),
-        ])
+        if not fused:
+            pack_d = torch.cat([
+                gain, feat.to(torch.float32), b.to(torch.float32),
+                left_stats.reshape(-1),
+            ])
         ev = None
         if bins.is_cuda:
             pack_h = torch.empty(pack_d.numel(), dtype=torch.float32,
@@ -931,7 +968,11 @@ def grow_forest(
         cid = cur_len[t_ids] + 2 * rank
         cur_len += 2 * counts
 
-        hists = hists.index_select(0, _to_dev_async(s_idx, device))
+        if fused:
+            # the level tensor stays as it is; the children point into it
+            parent_row_t = s_idx.repeat_interleave(2)
+        else:
+            hists = hists.index_select(0, _to_dev_async(s_idx, device))
 
         # ----- next level bookkeeping ------------------------------------
         # everything that depends only on the SPLIT results happens here,

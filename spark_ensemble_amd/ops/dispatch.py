@@ -167,7 +167,8 @@ def _hist_build_launch(m, bins, gh, row_idx, node_offsets, node_col0,
 
 
 def hist_build_forest(bins, gh, row_idx, node_offsets, node_col0, num_bins,
-                      c_per_node, max_abs, d_dims=1, gh_by_position=False):
+                      c_per_node, max_abs, d_dims=1, gh_by_position=False,
+                      identity_rows=False):
     """Forest histogram build: gh is [N, CH] with contiguous per-node
     channel groups; node_col0[n] selects the base column node n
     accumulates (tree fusion: owning_tree * C; wide-gini chunking: the
@@ -176,14 +177,17 @@ def hist_build_forest(bins, gh, row_idx, node_offsets, node_col0, num_bins,
     per-class futures, GBMClassifier.scala:377-411).  ``max_abs`` is
     slot-wise ([c_per_node]): max over the corresponding column of every
     group.  ``gh_by_position``: gh is the compact ``[len(row_idx), CH]``
-    matrix of ``gather_ranges_gh`` and entry i of row_idx reads gh row i."""
+    matrix of ``gather_ranges_gh`` and entry i of row_idx reads gh row i.
+    ``identity_rows``: row_idx is ``arange(N)`` (the root of a lone tree over
+    every row) and the GPU kernel does not read it."""
     if bins.is_cuda:
         m = _require_hip("hist_build")
         if m is not None:
             return _hist_build_launch(
                 m, bins, gh, row_idx, node_offsets,
                 node_col0.to(torch.int32).cpu().contiguous(), num_bins,
-                c_per_node, max_abs, d_dims, False, gh_by_position,
+                c_per_node, max_abs, d_dims, bool(identity_rows),
+                gh_by_position,
             )
     if gh_by_position:
         # the reference indexes gh by row: bins gathered, rows = positions
@@ -277,6 +281,105 @@ def split_search(hist, lam=1e-6, min_child_weight=0.0, min_instances=1.0, min_in
     return reference.split_search(hist, lam, min_child_weight, min_instances, min_info_gain, d_dims)
 
 
+def level_fused_enabled() -> bool:
+    """``SEA_LEVEL_FUSED=0`` keeps the tree level loop on the composed ops
+    (assemble + split_search + pack, device-side left counts); read at every
+    call."""
+    return os.environ.get("SEA_LEVEL_FUSED", "1") != "0"
+
+
+def _check_level_table(table, n_built, n_prev):
+    """The checks of the native level_split, for the composed path."""
+    tb = table.tolist()
+    n = len(tb)
+    for j, (br, pr, sr) in enumerate(tb):
+        if br >= 0:
+            if br >= n_built:
+                raise RuntimeError(f"level_split: built_row {br} of node {j} "
+                                   "out of range")
+            continue
+        if br != -1:
+            raise RuntimeError(f"level_split: built_row of node {j} is {br}")
+        if not 0 <= pr < n_prev:
+            raise RuntimeError(f"level_split: parent_row {pr} of node {j} "
+                               "out of range")
+        if not 0 <= sr < n_built:
+            raise RuntimeError(f"level_split: sibling_built_row {sr} of node "
+                               f"{j} out of range")
+        if (j ^ 1) >= n or tb[j ^ 1][0] != sr:
+            raise RuntimeError(f"level_split: the sibling of derived node {j} "
+                               f"is not the built node in row {sr}")
+
+
+def level_split(built, parent, table, lam=1e-6, min_child_weight=0.0,
+                min_instances=1.0, min_info_gain=0.0, d_dims=-1):
+    """Split search of one tree level straight off its sources.
+
+    ``built`` [n_built, F, B, C] holds the histograms built at this level,
+    ``parent`` [n_prev, F, B, C] the previous level's full tensor (None or
+    empty at the root), ``table`` a host int32 [n, 3] of (built_row,
+    parent_row, sibling_built_row) per active node: node j scans
+    ``built[built_row]`` when built_row >= 0, else ``parent[parent_row] -
+    built[sibling_built_row]``; its sibling is node j ^ 1.
+
+    Returns (level, pack, feat, bin): ``level`` [n, F, B, C] is the full level
+    tensor (``built`` itself at a root whose table is the identity), ``pack``
+    the f32 [n * (3 + C)] buffer (gain[n], feat[n], bin[n], left_stats[n, C])
+    meant for one copy to the host, feat / bin int32 device tensors for
+    ``partition_rows_async``.
+
+    GPU: one scan kernel + one decode kernel (C <= 8).  Without a GPU, or with
+    ``SEA_LEVEL_FUSED=0``, the same result is composed from index copies, a
+    subtraction, ``split_search`` and a cat.
+    """
+    table = table.to(torch.int32).cpu().contiguous()
+    n = table.shape[0]
+    n_built, F, B, C = built.shape
+    root = parent is None or parent.numel() == 0
+    n_prev = 0 if root else parent.shape[0]
+    if not root and tuple(parent.shape[1:]) != (F, B, C):
+        raise RuntimeError("level_split: parent and built disagree in F, B, C")
+    identity = n == n_built and bool(
+        (table[:, 0] == torch.arange(n, dtype=torch.int32)).all())
+    args = (float(lam), float(min_child_weight), float(min_instances),
+            float(min_info_gain))
+    if built.is_cuda and C <= 8 and level_fused_enabled():
+        m = _require_hip("level_split")
+        if m is not None:
+            dev = built.device
+            built = built.contiguous()
+            level = built if root and identity else torch.empty(
+                n, F, B, C, dtype=torch.float32, device=dev)
+            pack = torch.empty(n * (3 + C), dtype=torch.float32, device=dev)
+            feat = torch.empty(n, dtype=torch.int32, device=dev)
+            bin_ = torch.empty(n, dtype=torch.int32, device=dev)
+            m.level_split(
+                level, pack, feat, bin_, built,
+                built.new_empty(0) if root else parent.contiguous(), table,
+                int(d_dims), *args,
+            )
+            return level, pack, feat, bin_
+    _check_level_table(table, n_built, n_prev)
+    dev = built.device
+    if root and identity:
+        level = built
+    else:
+        tb = table.long()
+        b_nodes = (tb[:, 0] >= 0).nonzero(as_tuple=True)[0]
+        d_nodes = (tb[:, 0] < 0).nonzero(as_tuple=True)[0]
+        level = torch.empty(n, F, B, C, dtype=torch.float32, device=dev)
+        if b_nodes.numel():
+            level[b_nodes.to(dev)] = built[tb[b_nodes, 0].to(dev)]
+        if d_nodes.numel():
+            level[d_nodes.to(dev)] = (
+                parent[tb[d_nodes, 1].to(dev)] - built[tb[d_nodes, 2].to(dev)]
+            )
+    g, ft, b, ls = split_search(level, *args, d_dims=d_dims)
+    pack = torch.cat([g, ft.to(torch.float32), b.to(torch.float32),
+                      ls.reshape(-1)])
+    return level, pack, ft.to(torch.int32), b.to(torch.int32)
+
+
 def partition_rows(bins, row_idx, node_offsets, feat, thr):
     if bins.is_cuda:
         m = _require_hip("partition_rows")
@@ -330,12 +433,27 @@ def partition_rows_async(bins, row_idx, node_offsets, feat, thr):
     offs_cpu = node_offsets.to(torch.int64).cpu()
     row_idx = row_idx.to(torch.int32)
     new_rows = torch.empty_like(row_idx)
-    left_counts = torch.zeros(n, dtype=torch.int32, device=bins.device)
     f32 = feat.to(torch.int32).to(bins.device)
     t32 = thr.to(torch.int32).to(bins.device)
+    bt = _bins_transposed(bins)
+    if level_fused_enabled():
+        # the cursor table itself goes to the host (left = lcur - segment
+        # start, subtracted in partition_rows_finish): no zero fill, no
+        # segment-start upload, no device subtract; int32 feat / thr straight
+        # from level_split pass the two casts above untouched
+        cursors = m.partition_rows_cursors(
+            new_rows, bins, bt if bt is not None else _EMPTY_U8,
+            row_idx.contiguous(), offs_cpu, f32.contiguous(),
+            t32.contiguous(),
+        )
+        cur_h = torch.empty(n, 2, dtype=torch.int32, pin_memory=True)
+        cur_h.copy_(cursors, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return new_rows, (cur_h, ev), offs_cpu
+    left_counts = torch.zeros(n, dtype=torch.int32, device=bins.device)
     if _prof:
         _t1 = _time.perf_counter()
-    bt = _bins_transposed(bins)
     m.partition_rows(
         new_rows,
         left_counts,
@@ -436,7 +554,10 @@ def partition_rows_finish(new_rows, left_counts, offs_cpu):
     if isinstance(left_counts, tuple):
         lc_h, ev = left_counts
         ev.synchronize()
-        lc = lc_h.to(torch.int64)
+        if lc_h.dim() == 2:  # the cursor table: left = lcur - segment start
+            lc = lc_h[:, 0].to(torch.int64) - offs_cpu[:-1]
+        else:
+            lc = lc_h.to(torch.int64)
     else:
         lc = left_counts.cpu().to(torch.int64)
     sizes = torch.empty(2 * n, dtype=torch.int64)
