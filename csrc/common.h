@@ -1,4 +1,4 @@
-// Shared by csrc/ops.hip, csrc/linear.hip and csrc/wide_class.hip: argument
+// Shared by every csrc/*.hip: argument
 // checks, the pinned upload helper with its slot table, the sortable-float
 // encoding of the split scans, and the entry points that cross files.
 #pragma once
@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <tuple>
 
 #define CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be on GPU")
 #define CHECK_CONTIG(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -71,6 +72,16 @@ void forest_contrib(torch::Tensor out, torch::Tensor x, torch::Tensor ranges,
                     torch::Tensor path_v, torch::Tensor e_feat,
                     torch::Tensor e_lo, torch::Tensor e_hi, torch::Tensor e_z,
                     int64_t rows_per_tile, double scale);
+
+// csrc/forest_staged.hip
+void forest_staged_loss(torch::Tensor out, torch::Tensor partials,
+                        torch::Tensor x, torch::Tensor nodes,
+                        torch::Tensor tree_off, torch::Tensor groups,
+                        torch::Tensor init, torch::Tensor label,
+                        torch::Tensor weight, int64_t dim,
+                        int64_t max_group_nodes, int64_t loss_id,
+                        double param);
+std::tuple<int64_t, int64_t, int64_t> forest_staged_geometry();
 
 // csrc/linear.hip
 void logreg_loss_grad(torch::Tensor payload, torch::Tensor x, torch::Tensor y,

@@ -349,6 +349,8 @@ class GBMClassifier(ProbabilisticClassifier, _GBMClassifierParams):
             "rawPredictionCol", "probabilityCol",
         ):
             model.set(p, self.getOrDefault(p))
+        if self.getWeightCol():  # evaluateEachIteration weighs rows by it
+            model.set("weightCol", self.getWeightCol())
         return model
 
     # ---- fold-vectorized fitting (OOF stacking fast path) ----------------
@@ -508,6 +510,8 @@ class GBMClassifier(ProbabilisticClassifier, _GBMClassifierParams):
                 "rawPredictionCol", "probabilityCol",
             ):
                 model.set(p, self.getOrDefault(p))
+            if self.getWeightCol():
+                model.set("weightCol", self.getWeightCol())
             out.append(model)
         if include_full:
             return out[:-1], out[-1]
@@ -644,6 +648,33 @@ class GBMClassificationModel(ProbabilisticClassificationModel, _GBMClassifierPar
     @property
     def numModels(self) -> int:
         return len(self._models)
+
+    def evaluateEachIteration(self, dataset: TensorFrame, loss=None):
+        """Weighted mean loss on ``dataset`` after the init model alone
+        (entry 0) and after each boosting stage: a CPU float64 tensor of
+        length ``numModels + 1`` (Spark ML GBT ``evaluateEachIteration``).
+        ``loss``: None for the model's own loss, a classification loss
+        name, or a ``GBMLoss`` instance whose ``dim`` is the model's.  Row
+        weights come from ``weightCol`` when it is set and present.  With
+        built-in tree stages the whole curve is one fused pass over the
+        rows (docs/gbm.md, "Learning curves")."""
+        from ..boosting import staged
+
+        k = self._num_classes
+        loss = staged.resolve_loss(
+            self, loss, lambda name: get_classification_loss(name, k),
+            self._dim)
+        stages = list(zip(self._models, self._weights, self._subspaces))
+        return staged.evaluate_each_iteration(
+            self, dataset, loss, self._dim, stages,
+            lambda x: self._init.predictRaw(x)[:, : self._dim])
+
+    def truncate(self, n: int) -> "GBMClassificationModel":
+        """A new model keeping the init and the first ``n`` stages
+        (``0 <= n <= numModels``); stage models are shared, not copied."""
+        from ..boosting import staged
+
+        return staged.truncated(self, n)
 
     @property
     def featureImportances(self):

@@ -64,6 +64,31 @@ def slice_features(x: torch.Tensor, indices: torch.Tensor) -> torch.Tensor:
     return x.index_select(1, indices.to(x.device))
 
 
+def orig_space_features(m, sub, num_features):
+    """Split-feature ids of the built-in tree model ``m`` in the ORIGINAL
+    feature space: ``m._tree["feature"]`` itself under an identity (or
+    absent) subspace ``sub``, else the ids mapped through ``sub`` (leaves
+    keep their negative marker), built once and cached on the model as
+    ``_tree_orig_feats``.  The packed predictors, the contribution pack and
+    the staged evaluation walk the unsliced x with these."""
+    feat = m._tree["feature"]
+    identity = sub is None or (
+        sub.numel() == num_features
+        and bool((sub.cpu() == torch.arange(num_features)).all())
+    )
+    if identity:
+        return feat
+    remapped = getattr(m, "_tree_orig_feats", None)
+    if remapped is None:
+        fl = feat.long()
+        sub_dev = sub.to(fl.device)
+        remapped = torch.where(
+            fl >= 0, sub_dev[fl.clamp_min(0)], fl
+        ).to(torch.int32)
+        m._tree_orig_feats = remapped
+    return remapped
+
+
 def packed_forest_margin(x, models, weights, subspaces, num_features,
                          cache=None):
     """Batched ensemble inference fast path: when every stage model is a
@@ -84,20 +109,9 @@ def packed_forest_margin(x, models, weights, subspaces, num_features,
         if not isinstance(m, DecisionTreeRegressionModel):
             return None
         t = m._tree
-        identity = sub is None or (
-            sub.numel() == num_features
-            and bool((sub.cpu() == torch.arange(num_features)).all())
-        )
-        if not identity:
-            remapped = getattr(m, "_tree_orig_feats", None)
-            if remapped is None:
-                feat = t["feature"].long()
-                sub_dev = sub.to(feat.device)
-                remapped = torch.where(
-                    feat >= 0, sub_dev[feat.clamp_min(0)], feat.long()
-                ).to(torch.int32)
-                m._tree_orig_feats = remapped
-            t = dict(t, feature=remapped)
+        feat = orig_space_features(m, sub, num_features)
+        if feat is not t["feature"]:
+            t = dict(t, feature=feat)
         trees.append(t)
     w = torch.tensor([float(v) for v in weights], dtype=torch.float32)
     return _ops.forest_predict(x, trees, w, cache=cache).squeeze(1)
@@ -140,21 +154,7 @@ def packed_forest_vote(x, models, subspaces, num_features, soft,
             return None
         t = m._tree
         lv = _vote_leaves(m, soft)
-        identity = sub is None or (
-            sub.numel() == num_features
-            and bool((sub.cpu() == torch.arange(num_features)).all())
-        )
-        feat = t["feature"]
-        if not identity:
-            remapped = getattr(m, "_tree_orig_feats", None)
-            if remapped is None:
-                fl = feat.long()
-                sub_dev = sub.to(fl.device)
-                remapped = torch.where(
-                    fl >= 0, sub_dev[fl.clamp_min(0)], fl
-                ).to(torch.int32)
-                m._tree_orig_feats = remapped
-            feat = remapped
+        feat = orig_space_features(m, sub, num_features)
         trees.append(dict(t, feature=feat, leaf_value=lv))
     w = torch.ones(len(trees), dtype=torch.float32)
     return _ops.forest_predict(x, trees, w, cache=cache)
@@ -186,20 +186,9 @@ def packed_forest_contrib(x, models, weights, planes, subspaces, num_planes,
         t = m._tree
         if vote is not None:
             t = dict(t, leaf_value=_vote_leaves(m, vote == "soft"))
-        identity = sub is None or (
-            sub.numel() == num_features
-            and bool((sub.cpu() == torch.arange(num_features)).all())
-        )
-        if not identity:
-            remapped = getattr(m, "_tree_orig_feats", None)
-            if remapped is None:
-                fl = t["feature"].long()
-                sub_dev = sub.to(fl.device)
-                remapped = torch.where(
-                    fl >= 0, sub_dev[fl.clamp_min(0)], fl
-                ).to(torch.int32)
-                m._tree_orig_feats = remapped
-            t = dict(t, feature=remapped)
+        feat = orig_space_features(m, sub, num_features)
+        if feat is not m._tree["feature"]:
+            t = dict(t, feature=feat)
         trees.append(t)
     return _ops.forest_contrib(
         x, trees, [float(v) for v in weights], [int(p) for p in planes],

@@ -960,6 +960,135 @@ def forest_contrib(x, trees, weights=None, planes=None, num_planes=1,
     return reference.forest_contrib(x, trees, weights, planes, num_planes)
 
 
+# ---- per-stage loss curves (csrc/forest_staged.hip) -----------------------
+
+STAGED_MAX_DIM = 8
+
+# what the last forest_staged_loss call did: {"path": "native" |
+# "reference", "mode": "binned" | "raw" | None, "rows_per_lane": R,
+# "groups": G} (tests assert the route without guessing the policy)
+last_forest_staged_info: dict = {}
+
+
+def _staged_native_loss(loss, dim):
+    """(loss id, param) when the kernel has ``loss``'s device form, else
+    None: the nine built-in classes, dim > 1 only for logloss."""
+    from ..boosting import losses as _losses
+
+    builtin = {
+        "squared": _losses.SquaredLoss, "absolute": _losses.AbsoluteLoss,
+        "logcosh": _losses.LogCoshLoss,
+        "scaledlogcosh": _losses.ScaledLogCoshLoss,
+        "huber": _losses.HuberLoss, "quantile": _losses.QuantileLoss,
+        "logloss": _losses.LogLoss, "exponential": _losses.ExponentialLoss,
+        "bernoulli": _losses.BernoulliLoss,
+    }
+    if type(loss) is not builtin.get(getattr(loss, "name", None)):
+        return None
+    if loss.dim != dim or (dim > 1 and loss.name != "logloss"):
+        return None
+    return loss.loss_id, float(loss.param)
+
+
+def forest_staged_loss(x, trees, weights, dim, init, label, row_weight, loss,
+                       cache=None):
+    """Per-stage weighted loss sums ``[S + 1]`` float64 of a boosted forest
+    of ``S * dim`` scalar-leaf trees in stage-major order; semantics in
+    ``reference.forest_staged_loss``.  The result is on the device of x.
+
+    On the GPU one fused pass (csrc/forest_staged.hip) serves ``dim <=
+    STAGED_MAX_DIM`` when the forest packs as v2 (every tree within
+    ``_FP2_GROUP_NODES``) and the loss is one of the built-in nine;
+    anything else runs the torch reference op on the same device.  Rows
+    are read as u8 ranks (``bin_features`` against the pack's threshold
+    sets, as ``forest_predict2``) whenever the pack has them, else as f32;
+    ``SEA_STAGED_MODE=raw|binned`` overrides.  Both are exact.
+
+    ``cache``: caller-owned dict; the pack is built once per (forest,
+    device) and kept under "pack", as ``forest_predict`` keeps its own.
+    """
+    dim = int(dim)
+    if len(trees) % dim:
+        raise ValueError(
+            f"{len(trees)} trees are not whole stages of {dim} trees")
+    native = x.is_cuda and x.dtype == torch.float32 and dim <= STAGED_MAX_DIM
+    lp = _staged_native_loss(loss, dim) if native else None
+    m = _require_hip("forest_staged_loss") if lp is not None else None
+    if m is not None and any(t["leaf_value"].shape[1] != 1 for t in trees):
+        m = None
+    if m is not None:
+        N, F = x.shape
+        pack = None
+        if trees:
+            pack = cache.get("pack") if cache is not None else None
+            if (pack is None or pack["T"] != len(trees)
+                    or pack["dev"] != x.device):
+                w = torch.as_tensor(
+                    [float(v) for v in weights], dtype=torch.float32)
+                pack = _pack_forest(trees, w, x.device)
+                if cache is not None:
+                    cache["pack"] = pack
+            if "f_max" not in pack:
+                pack["f_max"] = int(pack["feats"].max())
+            if pack["f_max"] >= F:
+                raise ValueError(
+                    f"forest splits on feature {pack['f_max']} but x has "
+                    f"{F} columns")
+        if (pack is None or pack["v2"]) and 1 <= F < 32768 and N >= 1:
+            threads, rpl, _ = m.forest_staged_geometry()
+            S1 = len(trees) // dim + 1
+            n_slots = -(-N // (threads * rpl)) * (threads // 64)
+            out = torch.empty(S1, dtype=torch.float64, device=x.device)
+            partials = torch.empty(n_slots, S1, dtype=torch.float64,
+                                   device=x.device)
+            xc = x.contiguous()
+            mode = "raw"
+            if pack is None:
+                nodes = torch.empty(0, dtype=torch.int64, device=x.device)
+                tree_off = torch.empty(0, dtype=torch.int32, device=x.device)
+                groups = torch.empty(0, 4, dtype=torch.int32, device=x.device)
+                max_nodes = 0
+            else:
+                binned_avail = bool(
+                    pack.get("binned_ok") and pack["bin_fmax"] <= F)
+                env_mode = os.environ.get("SEA_STAGED_MODE")
+                if binned_avail and env_mode != "raw":
+                    mode = "binned"
+                elif env_mode == "binned":
+                    raise ValueError(
+                        "SEA_STAGED_MODE=binned: this forest has no u8 rank "
+                        "form (a feature with more than 255 thresholds, or "
+                        "no split at all)")
+                tree_off, groups = pack["offsets32"], pack["groups_t"]
+                max_nodes = pack["max_nodes"]
+                if mode == "binned":
+                    nodes = pack["node64b"]
+                    xb = torch.empty(xc.shape, dtype=torch.uint8,
+                                     device=x.device)
+                    m.bin_features(xb, xc, _binned_edges(pack, F))
+                    xc = xb
+                else:
+                    nodes = pack["node64"]
+
+            def f32(t, shape):
+                return t.to(x.device, torch.float32).reshape(shape).contiguous()
+
+            m.forest_staged_loss(
+                out, partials, xc, nodes, tree_off, groups,
+                f32(init, (N, dim)), f32(label, (N, dim)),
+                f32(row_weight, (N,)), dim, int(max_nodes), int(lp[0]),
+                float(lp[1]),
+            )
+            last_forest_staged_info.update(
+                path="native", mode=mode, rows_per_lane=int(rpl),
+                groups=int(groups.shape[0]))
+            return out
+    last_forest_staged_info.update(path="reference", mode=None,
+                                   rows_per_lane=0, groups=0)
+    return reference.forest_staged_loss(
+        x, trees, weights, dim, init, label, row_weight, loss)
+
+
 def logreg_loss_grad(x, y_int, w, wmat, has_bias):
     """Single-pass fused logistic loss+gradient.
 

@@ -369,6 +369,40 @@ def forest_predict(
     return out
 
 
+def forest_staged_loss(x, trees, weights, dim, init, label, row_weight, loss):
+    """Per-stage loss sums of a boosted forest: ``[S + 1]`` float64.
+
+    ``trees`` holds ``S * dim`` scalar-leaf trees in stage-major order: tree
+    t belongs to stage ``t // dim`` and adds ``weights[t] * leaf`` to margin
+    column ``t % dim``.  Entry 0 is ``sum_i w_i * loss(label_i, init_i)``
+    with ``init`` the ``[N, dim]`` start margins, entry s the same sum after
+    the first s stages (sums, not means).  ``label`` is the encoded label
+    ``[N, dim]``, ``loss`` a ``GBMLoss``.
+
+    Runs in the dtype of ``x``: margins and the per-row weighted loss are
+    in that dtype, the sum over rows is always float64.  ``x.double()``
+    gives the float64 oracle, ``x.float()`` the f32 reference.  The result
+    is on the device of ``x``."""
+    dt = x.dtype
+    dim = int(dim)
+    if len(trees) % dim:
+        raise ValueError(
+            f"{len(trees)} trees are not whole stages of {dim} trees")
+    margin = init.to(dt).reshape(x.shape[0], dim).clone()
+    lab = label.to(dt).reshape(x.shape[0], dim)
+    w = row_weight.to(dt)
+    out = [(loss.loss(lab, margin) * w).double().sum()]
+    for t, tree in enumerate(trees):
+        leaf = tree_predict(
+            x, *(tree[k].to(x.device) for k in
+                 ("feature", "threshold", "left_child", "leaf_value")), 64,
+        )[:, 0].to(dt)
+        margin[:, t % dim] += leaf * float(weights[t])
+        if t % dim == dim - 1:
+            out.append((loss.loss(lab, margin) * w).double().sum())
+    return torch.stack(out)
+
+
 def logreg_loss_grad(x, y_int, w, wmat, has_bias):
     """Torch reference for the fused logistic loss+grad payload
     (dispatch.logreg_loss_grad contract)."""

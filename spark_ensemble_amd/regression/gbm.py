@@ -300,8 +300,11 @@ class GBMRegressor(Regressor, _GBMRegressorParams):
         model._weights = weights[:keep]
         model._subspaces = [s for s in subspaces[:keep]]
         model._num_features = num_features
-        for p in ("featuresCol", "labelCol", "predictionCol"):
+        # loss and alpha: what evaluateEachIteration(loss=None) evaluates
+        for p in ("featuresCol", "labelCol", "predictionCol", "loss", "alpha"):
             model.set(p, self.getOrDefault(p))
+        if self.getWeightCol():  # ... and the rows' weights
+            model.set("weightCol", self.getWeightCol())
         return model
 
     # ---- fold-vectorized fitting (OOF stacking fast path) ----------------
@@ -427,8 +430,11 @@ class GBMRegressor(Regressor, _GBMRegressorParams):
             model._weights = [float(v) for v in stage_w[:, t]]
             model._subspaces = [ident] * k_stages
             model._num_features = num_features
-            for p in ("featuresCol", "labelCol", "predictionCol"):
+            for p in ("featuresCol", "labelCol", "predictionCol", "loss",
+                      "alpha"):
                 model.set(p, self.getOrDefault(p))
+            if self.getWeightCol():
+                model.set("weightCol", self.getWeightCol())
             out.append(model)
         if include_full:
             return out[:-1], out[-1]
@@ -508,6 +514,34 @@ class GBMRegressionModel(RegressionModel, _GBMRegressorParams):
     @property
     def numModels(self) -> int:
         return len(self._models)
+
+    def evaluateEachIteration(self, dataset: TensorFrame, loss=None):
+        """Weighted mean loss on ``dataset`` after the init model alone
+        (entry 0) and after each boosting stage: a CPU float64 tensor of
+        length ``numModels + 1`` (Spark ML GBT ``evaluateEachIteration``).
+        ``loss``: None for the model's own loss, a regression loss name
+        (built with the model's alpha), or a ``GBMLoss`` instance.  Huber's
+        delta is not stored on the model: pass ``HuberLoss(delta)``.  Row
+        weights come from ``weightCol`` when it is set and present.  With
+        built-in tree stages the whole curve is one fused pass over the
+        rows (docs/gbm.md, "Learning curves")."""
+        from ..boosting import staged
+
+        alpha = self.getOrDefault("alpha")
+        loss = staged.resolve_loss(
+            self, loss, lambda name: get_regression_loss(name, alpha=alpha), 1)
+        stages = [([m], [wt], sub) for m, wt, sub in
+                  zip(self._models, self._weights, self._subspaces)]
+        return staged.evaluate_each_iteration(
+            self, dataset, loss, 1, stages,
+            lambda x: self._init.predict(x).unsqueeze(1))
+
+    def truncate(self, n: int) -> "GBMRegressionModel":
+        """A new model keeping the init and the first ``n`` stages
+        (``0 <= n <= numModels``); stage models are shared, not copied."""
+        from ..boosting import staged
+
+        return staged.truncated(self, n)
 
     @property
     def featureImportances(self):
