@@ -78,6 +78,8 @@ def bin_features(x, edges):
         m = _require_hip("bin_features")
         if m is not None:
             out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+            if x.shape[0] == 0:
+                return out  # a 0-block grid is not a valid launch
             m.bin_features(out, x.contiguous(), edges.contiguous())
             return out
     return reference.bin_features(x, edges)
@@ -575,6 +577,8 @@ def tree_predict(x, feature, threshold, left_child, leaf_value, max_depth):
             N = x.shape[0]
             D = leaf_value.shape[1]
             out = torch.empty(N, D, dtype=torch.float32, device=x.device)
+            if N == 0:
+                return out
             m.tree_predict(
                 out,
                 x.contiguous(),
@@ -597,6 +601,9 @@ def forest_predict(x, trees, weights=None, max_depth=64, cache=None):
     if x.is_cuda and trees:
         m = _require_hip("forest_predict")
         if m is not None:
+            if x.shape[0] == 0:
+                return torch.zeros(0, trees[0]["leaf_value"].shape[1],
+                                   dtype=torch.float32, device=x.device)
             pack = cache.get("pack") if cache is not None else None
             if pack is None or pack["T"] != len(trees) or pack["dev"] != x.device:
                 pack = _pack_forest(trees, weights, x.device)
@@ -684,10 +691,11 @@ def _pack_forest_binned(pack, feats, thrs, payload):
     """Rank-transform serving structures (EXACT): collect each feature's
     sorted unique threshold set; a node's threshold becomes its RANK in
     that set, and at predict time every row is rank-transformed once via
-    the bin_features kernel (lower_bound against the padded set), after
-    which  x <= thr  <=>  rank(x) <= rank(thr)  on u8 bins — rows shrink
-    4x for the divergent walk gathers.  Disabled when any feature carries
-    > 255 distinct thresholds (u8 overflow)."""
+    the bin_features kernel (lower_bound against the +inf-padded set),
+    after which  x <= thr  <=>  rank(x) <= rank(thr)  on u8 bins for every
+    f32 x, +-inf included; a NaN x ranks above every threshold and goes
+    right — rows shrink 4x for the divergent walk gathers.  Disabled when
+    any feature carries > 255 distinct thresholds (u8 overflow)."""
     dev = pack["dev"]
     mask = feats >= 0
     m_cnt = int(mask.sum())
@@ -695,6 +703,10 @@ def _pack_forest_binned(pack, feats, thrs, payload):
         return
     f_int = feats[mask].long()
     t_val = thrs[mask]
+    if bool(torch.isnan(t_val).any()):
+        # x <= NaN is false for every x; a NaN has no place in a sorted
+        # edge row, so such a forest keeps the raw walk
+        return
     f_max = int(f_int.max()) + 1
     # sort by (feature, threshold)
     order = torch.argsort(t_val)
@@ -735,13 +747,16 @@ def _pack_forest_binned(pack, feats, thrs, payload):
 
 def _binned_edges(pack, F):
     """[F, maxcnt] padded per-feature threshold sets for bin_features
-    (pad = +3e38 so lower_bound is unaffected); cached per F."""
+    (pad = +inf: no threshold sorts above it, so every row stays sorted
+    and lower_bound is unaffected — x = +inf gets the rank of a +inf
+    threshold if the feature has one, else the count, and NaN still gets
+    maxcnt); cached per F."""
     cached = pack.get("bedges")
     if cached is not None and cached.shape[0] == F:
         return cached
     dev = pack["dev"]
     mc = pack["bin_maxcnt"]
-    edges = torch.full((F, mc), 3.0e38, dtype=torch.float32, device=dev)
+    edges = torch.full((F, mc), float("inf"), dtype=torch.float32, device=dev)
     fu, tu, offs = pack["bin_fu"], pack["bin_tu"], pack["bin_offs"]
     col = torch.arange(fu.numel(), device=dev) - offs[fu]
     edges[fu, col] = tu
@@ -782,6 +797,8 @@ _SERVE_MODES = ("binned_t", "binned", "raw")
 
 def _forest_predict_packed(m, x, pack):
     D = pack["D"]
+    if x.shape[0] == 0:  # no launch: every kernel here sizes its grid by N
+        return torch.zeros(0, D, dtype=torch.float32, device=x.device)
     if pack["v2"] and x.shape[1] < 32768 and hasattr(m, "forest_predict2"):
         xc = x.contiguous()
         env_mode = os.environ.get("SEA_SERVE_MODE")

@@ -83,7 +83,13 @@ def quantile_bins(
     q = torch.arange(1, max_bins, device=x.device, dtype=torch.float32) / max_bins
     pos = (q * (s - 1)).long().clamp_(0, s - 1)
     edges = xs_sorted.index_select(0, pos).T.contiguous()  # [F, B-1]
-    return edges
+    # NaNs sort last, so a column with many of them would end its cut
+    # points in NaN: the bin search would treat those as below every x
+    # (merging real values with the NaN bin) and a split there would get a
+    # NaN threshold, which sends every row right when serving.  +inf keeps
+    # the row sorted and  bin <= t  <=>  x <= edges[t]  for every x; a NaN
+    # x still lands in the last bin.
+    return edges.masked_fill_(edges.isnan(), float("inf"))
 
 
 def bin_features(x: torch.Tensor, edges: torch.Tensor) -> torch.Tensor:
