@@ -83,6 +83,13 @@ void forest_staged_loss(torch::Tensor out, torch::Tensor partials,
                         double param);
 std::tuple<int64_t, int64_t, int64_t> forest_staged_geometry();
 
+// csrc/forest_oob.hip
+void forest_oob(torch::Tensor sums, torch::Tensor counts, torch::Tensor x,
+                torch::Tensor nodes, torch::Tensor leaves,
+                torch::Tensor tree_off, torch::Tensor groups,
+                torch::Tensor mask, int64_t dim, int64_t max_group_nodes);
+std::tuple<int64_t, int64_t, int64_t> forest_oob_geometry();
+
 // csrc/linear.hip
 void logreg_loss_grad(torch::Tensor payload, torch::Tensor x, torch::Tensor y,
                       torch::Tensor w, torch::Tensor wmat, bool has_bias);

@@ -2214,6 +2214,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-stage weighted loss sums of a packed boosted forest");
   m.def("forest_staged_geometry", &forest_staged_geometry,
         "(threads, rows per lane, grid cap) of forest_staged_loss");
+  m.def("forest_oob", &forest_oob,
+        "out-of-bag leaf sums and counts of a packed forest under a mask");
+  m.def("forest_oob_geometry", &forest_oob_geometry,
+        "(threads, rows per lane, grid cap) of forest_oob");
   m.def("transpose_u8", &transpose_u8, "tiled u8 matrix transpose");
   m.def("gather_ranges", &gather_ranges,
         "one-pass concat of contiguous index ranges");

@@ -19,11 +19,12 @@ from .. import persistence
 from ..ensemble.binning import BinnedDataset
 from ..ensemble.params import (
     HasBaseLearner,
+    HasComputeOob,
     HasNumBaseLearners,
     HasParallelism,
     HasSubBag,
 )
-from ..ensemble.utils import slice_features, subspace
+from ..ensemble.utils import OobResults, slice_features, subspace
 from ..estimator import (
     ProbabilisticClassificationModel,
     ProbabilisticClassifier,
@@ -56,7 +57,8 @@ class _BaggingClassifierParams(
         return self.set("seed", v)
 
 
-class BaggingClassifier(ProbabilisticClassifier, _BaggingClassifierParams):
+class BaggingClassifier(ProbabilisticClassifier, _BaggingClassifierParams,
+                        HasComputeOob):
     def _default_base_learner(self):
         from ..models.tree import DecisionTreeClassifier
 
@@ -80,6 +82,7 @@ class BaggingClassifier(ProbabilisticClassifier, _BaggingClassifierParams):
             DecisionTreeClassifier, _class_mode_ok, fit_class_tree_forest,
         )
 
+        oob = self.getComputeOob()
         # 7..32 classes fuse too on the GPU (the grower's class mode)
         wide_fused = x.is_cuda and _class_mode_ok(num_classes)
         if (
@@ -122,6 +125,9 @@ class BaggingClassifier(ProbabilisticClassifier, _BaggingClassifierParams):
                 "rawPredictionCol", "probabilityCol",
             ):
                 model.set(p, self.getOrDefault(p))
+            if oob:
+                model._oob = self._oob_estimates(
+                    x, y, w, models, subspaces, bag_w > 0, num_classes, comm)
             return model
 
         if learner is not None and learner.hasParam("maxBins"):
@@ -139,13 +145,18 @@ class BaggingClassifier(ProbabilisticClassifier, _BaggingClassifierParams):
                     comm.rank,
                 )
                 fr = binned.fit_frame(learner, y, bag_w, subspaces[i])
-                return self.fit_base_learner(learner, fr, weight_col="weight")
+                fitted = self.fit_base_learner(learner, fr, weight_col="weight")
+                return (fitted, bag_w > 0) if oob else fitted
             return task
 
         from ..parallel.streams import parallel_fits
 
         models = parallel_fits([fit_one(i) for i in range(k)],
                                self.getParallelism())
+        inbag = None
+        if oob:
+            inbag = torch.stack([b for _, b in models], dim=1)
+            models = [m for m, _ in models]
 
         model = BaggingClassificationModel()
         model._models = models
@@ -158,7 +169,63 @@ class BaggingClassifier(ProbabilisticClassifier, _BaggingClassifierParams):
             "rawPredictionCol", "probabilityCol",
         ):
             model.set(p, self.getOrDefault(p))
+        if oob:
+            model._oob = self._oob_estimates(
+                x, y, w, models, subspaces, inbag, num_classes, comm)
         return model
+
+    def _oob_estimates(self, x, y, w, models, subspaces, inbag, num_classes,
+                       comm):
+        """Out-of-bag votes of the training rows and their weighted
+        accuracy: member i votes on row r only where ``not inbag[r, i]``,
+        under the estimator's voting strategy.  Tree members are one
+        ``forest_oob`` pass; anything else is a loop over the members in
+        order.  A row of instance weight 0 is out of every bag: it gets a
+        prediction and weighs nothing in the score.  The score and the
+        coverage are sums over all ranks, in float64."""
+        from ..ensemble.utils import oob_weighted_sums, packed_forest_oob
+
+        soft = self.getVotingStrategy() == "soft"
+        res = packed_forest_oob(x, models, subspaces, x.shape[1], inbag,
+                                vote="soft" if soft else "hard")
+        if res is not None:
+            raw, counts = res
+        else:
+            n = x.shape[0]
+            raw = torch.zeros(n, num_classes, dtype=torch.float32,
+                              device=x.device)
+            counts = torch.zeros(n, dtype=torch.int32, device=x.device)
+            zero = torch.zeros((), dtype=torch.float32, device=x.device)
+            for i, (sub, m) in enumerate(zip(subspaces, models)):
+                out = ~inbag[:, i]
+                xs = slice_features(x, sub)
+                if soft:
+                    if not hasattr(m, "predictProbability"):
+                        raise RuntimeError(
+                            "soft voting requires probabilistic base models "
+                            "(reference BaggingClassifier.scala:275-277)"
+                        )
+                    raw = raw + torch.where(
+                        out[:, None], m.predictProbability(xs).float(), zero)
+                else:
+                    pred = m.predict(xs).long()
+                    raw.scatter_add_(1, pred.unsqueeze(1),
+                                     out.float().unsqueeze(1))
+                counts += out.to(torch.int32)
+        has = counts > 0
+        nan = torch.full((), float("nan"), dtype=torch.float32,
+                         device=x.device)
+        prob = torch.where(has[:, None], raw / counts[:, None], nan)
+        pred = torch.where(has, raw.argmax(dim=1).float(), nan)
+        wc = torch.where(has, w, torch.zeros_like(w))
+        s_all, s_w, s_hit = oob_weighted_sums(
+            comm, [w, wc, wc * (pred == y).float()])
+        return {
+            "oobRawPrediction": raw, "oobProbability": prob,
+            "oobPrediction": pred, "oobCounts": counts,
+            "oobScore": s_hit / s_w if s_w > 0 else float("nan"),
+            "oobCoverage": s_w / s_all if s_all > 0 else float("nan"),
+        }
 
     def _save_impl(self, path: str):
         persistence.save_metadata(self, path)
@@ -169,8 +236,18 @@ class BaggingClassifier(ProbabilisticClassifier, _BaggingClassifierParams):
 
 
 class BaggingClassificationModel(
-    ProbabilisticClassificationModel, _BaggingClassifierParams
+    ProbabilisticClassificationModel, _BaggingClassifierParams, OobResults
 ):
+    @property
+    def oobRawPrediction(self):
+        """``[N, K]`` vote sums of the members that left the row out."""
+        return self._oob_get("oobRawPrediction")
+
+    @property
+    def oobProbability(self):
+        """``oobRawPrediction / oobCounts``; NaN rows where the count is 0."""
+        return self._oob_get("oobProbability")
+
     @property
     def models(self):
         return list(self._models)
@@ -266,6 +343,7 @@ class BaggingClassificationModel(
                 "numClasses": self._num_classes,
                 "numModels": len(self._models),
                 "numFeatures": self._num_features,
+                **self._oob_meta(),
             },
         )
         for i, m in enumerate(self._models):
@@ -278,6 +356,7 @@ class BaggingClassificationModel(
     def _load_extra(self, path: str, meta: dict):
         self._num_classes = meta["numClasses"]
         self._num_features = meta.get("numFeatures", -1)
+        self._load_oob(meta)
         self._models = []
         self._subspaces = []
         i = 0

@@ -216,6 +216,26 @@ class HasAggregationDepth(Params):
         return self.set("aggregationDepth", v)
 
 
+class HasComputeOob(Params):
+    """Out-of-bag estimates of a bagging fit (docs/bagging.md).  A param of
+    the estimators only: the fitted models carry the results, not the
+    switch, so their saved metadata is unchanged when it is off."""
+
+    def _declare_params(self):
+        super()._declare_params()
+        self.computeOob = self._bool_param(
+            "computeOob",
+            "compute out-of-bag predictions, score and coverage during fit",
+        )
+        self._setDefault(computeOob=False)
+
+    def getComputeOob(self):
+        return self.getOrDefault("computeOob")
+
+    def setComputeOob(self, v):
+        return self.set("computeOob", v)
+
+
 class HasSubBag(Params):
     """Row resampling + feature subspace params (reference HasSubBag.scala)."""
 

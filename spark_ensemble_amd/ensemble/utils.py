@@ -160,6 +160,90 @@ def packed_forest_vote(x, models, subspaces, num_features, soft,
     return _ops.forest_predict(x, trees, w, cache=cache)
 
 
+def packed_forest_oob(x, models, subspaces, num_features, inbag, vote=None,
+                      cache=None):
+    """Out-of-bag sums and counts of a bagged ensemble of built-in trees as
+    ONE ``forest_oob`` call: ``(sums [N, D] f32, counts [N] int32)``, member
+    i left out of row r's sum where ``inbag[r, i]``.  Regression trees
+    (``vote=None``) add their leaf value; classification trees add the
+    per-node leaf transform of ``packed_forest_vote`` (``vote`` "soft" /
+    "hard"), so the sums are the vote sums of the out-of-bag members.
+    Subspaced members walk the unsliced x through the ``_tree_orig_feats``
+    remap.  Returns None when a member is not such a tree."""
+    from ..models.tree import (
+        DecisionTreeClassificationModel, DecisionTreeRegressionModel)
+    from ..ops import dispatch as _ops
+
+    if not models:
+        return None
+    kind = (DecisionTreeRegressionModel if vote is None
+            else DecisionTreeClassificationModel)
+    trees = []
+    for m, sub in zip(models, subspaces):
+        if not isinstance(m, kind):
+            return None
+        t = m._tree
+        if vote is not None:
+            t = dict(t, leaf_value=_vote_leaves(m, vote == "soft"))
+        feat = orig_space_features(m, sub, num_features)
+        if feat is not m._tree["feature"]:
+            t = dict(t, feature=feat)
+        trees.append(t)
+    return _ops.forest_oob(x, trees, inbag, cache=cache)
+
+
+def oob_weighted_sums(comm, terms):
+    """float64 sums over the rows of every rank of each ``[N]`` tensor in
+    ``terms``: one all-reduce, so every rank gets the same numbers."""
+    s = torch.stack([t.double().sum() for t in terms])
+    return comm.all_reduce_(s, "sum").tolist()
+
+
+class OobResults:
+    """Out-of-bag results of a bagging model (docs/bagging.md).  ``_oob`` is
+    None for a model fitted without ``computeOob``.  The per-row tensors are
+    training-set-sized and rank-local, and are not saved; the score and the
+    coverage go into the saved metadata, so a loaded model answers those two
+    and None for the rest."""
+
+    _oob = None
+    _OOB_SAVED = ("oobScore", "oobCoverage")
+
+    def _oob_get(self, key):
+        return None if self._oob is None else self._oob.get(key)
+
+    @property
+    def oobPrediction(self):
+        """``[N]`` f32 out-of-bag prediction of every training row, NaN
+        where no member left the row out."""
+        return self._oob_get("oobPrediction")
+
+    @property
+    def oobCounts(self):
+        """``[N]`` int32: the members that left the row out of their bag."""
+        return self._oob_get("oobCounts")
+
+    @property
+    def oobScore(self):
+        """Weighted R^2 (regression) or accuracy (classification) of the
+        out-of-bag predictions over the rows that have one; NaN if none."""
+        return self._oob_get("oobScore")
+
+    @property
+    def oobCoverage(self):
+        """Weighted share of the rows with an out-of-bag prediction."""
+        return self._oob_get("oobCoverage")
+
+    def _oob_meta(self):
+        if self._oob is None:
+            return {}
+        return {k: self._oob[k] for k in self._OOB_SAVED}
+
+    def _load_oob(self, meta):
+        if all(k in meta for k in self._OOB_SAVED):
+            self._oob = {k: float(meta[k]) for k in self._OOB_SAVED}
+
+
 def packed_forest_contrib(x, models, weights, planes, subspaces, num_planes,
                           vote=None, cache=None):
     """Per-row feature contributions of an ensemble of built-in trees as ONE

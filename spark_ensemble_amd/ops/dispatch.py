@@ -1106,6 +1106,131 @@ def forest_staged_loss(x, trees, weights, dim, init, label, row_weight, loss,
         x, trees, weights, dim, init, label, row_weight, loss)
 
 
+# ---- out-of-bag sums and counts (csrc/forest_oob.hip) ---------------------
+
+OOB_MAX_DIM = 8
+_OOB_PACK_ROWS = 1 << 20  # rows per step of the mask packing (256 MiB of i64)
+
+# what the last forest_oob call did: {"path": "native" | "reference",
+# "mode": "binned" | "raw" | None, "rows_per_lane": R, "groups": G}
+last_forest_oob_info: dict = {}
+
+
+def _pack_inbag(inbag):
+    """``[N, T]`` bool -> ``[ceil(T / 32), N]`` int32: word ``t >> 5``, bit
+    ``t & 31`` set where row i is in tree t's bag.  Word-major, so
+    consecutive lanes of the kernel read consecutive words.  Built in int64
+    and wrapped to int32 (bit 31 is the sign bit)."""
+    N, T = inbag.shape
+    W = -(-T // 32)
+    out = torch.empty(W, N, dtype=torch.int32, device=inbag.device)
+    shifts = torch.arange(32, dtype=torch.int64, device=inbag.device)
+    for wd in range(W):
+        cols = inbag[:, wd * 32:(wd + 1) * 32]
+        for r0 in range(0, N, _OOB_PACK_ROWS):
+            c = cols[r0:r0 + _OOB_PACK_ROWS].to(torch.int64)
+            v = (c << shifts[:c.shape[1]]).sum(dim=1)
+            v = torch.where(v >= 2 ** 31, v - 2 ** 32, v)
+            out[wd, r0:r0 + _OOB_PACK_ROWS] = v.to(torch.int32)
+    return out
+
+
+def forest_oob(x, trees, inbag, cache=None):
+    """Out-of-bag leaf sums ``[N, D]`` f32 and counts ``[N]`` int32 of a
+    bagged forest under the ``[N, T]`` bool mask ``inbag`` (True: row i was
+    in tree t's bag); semantics in ``reference.forest_oob``.  No tree
+    weights.  Both results are on the device of x.
+
+    On the GPU one pass (csrc/forest_oob.hip) computes both; a lane skips
+    the walk of a tree whose bag held its row.  It serves f32 rows, ``D <= OOB_MAX_DIM`` and forests
+    that pack as v2 (every tree within ``_FP2_GROUP_NODES``); anything else
+    runs the torch reference op on the same device.  Rows are read as u8
+    ranks (``bin_features`` against the pack's threshold sets, as
+    ``forest_predict2``) whenever the pack has them, else as f32;
+    ``SEA_OOB_MODE=raw|binned`` overrides.  Both are exact.
+
+    ``cache``: caller-owned dict; the pack (tree weights all 1.0) is built
+    once per (forest, device) and kept under "pack".  Keep a dict of its
+    own for this op: the other forest ops reuse whatever pack they find
+    under that key by tree count and device alone, and theirs carry tree
+    weights.  A weighted pack found here is not used (and not replaced),
+    so sharing costs a pack per call here and wrong weights there.
+    """
+    if not trees:
+        raise ValueError("forest_oob needs at least one tree")
+    N, F = x.shape
+    inbag = torch.as_tensor(inbag)
+    if inbag.dim() != 2 or tuple(inbag.shape) != (N, len(trees)):
+        raise ValueError(
+            f"inbag is {tuple(inbag.shape)}, expected ({N}, {len(trees)})")
+    D = trees[0]["leaf_value"].shape[1]
+    # N == 0 launches nothing and packs nothing: the reference route below
+    # returns the empty tensors
+    native = (x.is_cuda and x.dtype == torch.float32 and D <= OOB_MAX_DIM
+              and N >= 1)
+    m = _require_hip("forest_oob") if native else None
+    if m is not None:
+        pack = cache.get("pack") if cache is not None else None
+        fits = (pack is not None and pack["T"] == len(trees)
+                and pack["dev"] == x.device)
+        if not (fits and pack.get("unit_weights")):
+            pack = _pack_forest(trees, None, x.device)
+            pack["unit_weights"] = True
+            # a weighted pack of the same forest belongs to another op
+            # (forest_predict folds tree weights into the D == 1 payload):
+            # it is neither used here nor replaced
+            if cache is not None and not fits:
+                cache["pack"] = pack
+        if "f_max" not in pack:
+            pack["f_max"] = int(pack["feats"].max())
+        if pack["f_max"] >= F:
+            raise ValueError(
+                f"forest splits on feature {pack['f_max']} but x has "
+                f"{F} columns")
+        if pack["v2"] and 1 <= F < 32768:
+            _, rpl, _ = m.forest_oob_geometry()
+            binned_avail = bool(
+                pack.get("binned_ok") and pack["bin_fmax"] <= F)
+            env_mode = os.environ.get("SEA_OOB_MODE")
+            mode = "raw"
+            if binned_avail and env_mode != "raw":
+                mode = "binned"
+            elif env_mode == "binned":
+                raise ValueError(
+                    "SEA_OOB_MODE=binned: this forest has no u8 rank form "
+                    "(a feature with more than 255 thresholds, or no split "
+                    "at all)")
+            xc = x.contiguous()
+            if mode == "binned":
+                nodes = pack["node64b"]
+                xb = torch.empty(xc.shape, dtype=torch.uint8, device=x.device)
+                m.bin_features(xb, xc, _binned_edges(pack, F))
+                xc = xb
+            else:
+                nodes = pack["node64"]
+            mask = _pack_inbag(inbag.to(x.device, torch.bool))
+            sums = torch.empty(N, D, dtype=torch.float32, device=x.device)
+            counts = torch.empty(N, dtype=torch.int32, device=x.device)
+            groups = pack["groups_t"]
+            m.forest_oob(sums, counts, xc, nodes, pack["leaves"],
+                         pack["offsets32"], groups, mask, D,
+                         int(pack["max_nodes"]))
+            last_forest_oob_info.update(
+                path="native", mode=mode, rows_per_lane=int(rpl),
+                groups=int(groups.shape[0]))
+            return sums, counts
+    last_forest_oob_info.update(path="reference", mode=None,
+                                rows_per_lane=0, groups=0)
+    f_max = max(int(t["feature"].max()) for t in trees)
+    if f_max >= F:
+        raise ValueError(
+            f"forest splits on feature {f_max} but x has {F} columns")
+    if x.shape[0] == 0:
+        return (torch.empty(0, D, dtype=x.dtype, device=x.device),
+                torch.empty(0, dtype=torch.int32, device=x.device))
+    return reference.forest_oob(x, trees, inbag)
+
+
 def logreg_loss_grad(x, y_int, w, wmat, has_bias):
     """Single-pass fused logistic loss+gradient.
 

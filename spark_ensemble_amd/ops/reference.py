@@ -409,6 +409,45 @@ def forest_staged_loss(x, trees, weights, dim, init, label, row_weight, loss):
     return torch.stack(out)
 
 
+def forest_oob(x, trees, inbag):
+    """Out-of-bag leaf sums and counts of a bagged forest.
+
+    ``x`` is ``[N, F]``, ``trees`` T tree dicts with D-wide leaves, ``inbag``
+    ``[N, T]`` bool, True where row i was in tree t's bag::
+
+        sums[i, :] = sum over t with not inbag[i, t], t = 0 .. T-1 in order,
+                     of leaf_t(x_i)                              [N, D]
+        counts[i]  = number of t with not inbag[i, t]            int32 [N]
+
+    There are no tree weights.  Routing is serving's (``x <= thr`` goes
+    left, a NaN goes right).  A row that is in every bag gets ``sums = 0,
+    counts = 0``.
+
+    Runs in the dtype of ``x``: ``x.double()`` gives the float64 oracle,
+    ``x.float()`` the f32 reference.  Both results are on the device of
+    ``x``."""
+    if not trees:
+        raise ValueError("forest_oob needs at least one tree")
+    dt = x.dtype
+    N = x.shape[0]
+    inbag = torch.as_tensor(inbag).to(x.device, torch.bool)
+    if inbag.dim() != 2 or tuple(inbag.shape) != (N, len(trees)):
+        raise ValueError(
+            f"inbag is {tuple(inbag.shape)}, expected ({N}, {len(trees)})")
+    D = trees[0]["leaf_value"].shape[1]
+    sums = torch.zeros(N, D, dtype=dt, device=x.device)
+    zero = torch.zeros((), dtype=dt, device=x.device)
+    for t, tree in enumerate(trees):
+        leaf = tree_predict(
+            x, *(tree[k].to(x.device) for k in
+                 ("feature", "threshold", "left_child", "leaf_value")), 64,
+        ).to(dt)
+        oob = ~inbag[:, t]
+        sums = sums + torch.where(oob[:, None], leaf, zero)
+    counts = (~inbag).sum(dim=1).to(torch.int32)
+    return sums, counts
+
+
 def logreg_loss_grad(x, y_int, w, wmat, has_bias):
     """Torch reference for the fused logistic loss+grad payload
     (dispatch.logreg_loss_grad contract)."""

@@ -29,11 +29,12 @@ from .. import persistence
 from ..ensemble.binning import BinnedDataset
 from ..ensemble.params import (
     HasBaseLearner,
+    HasComputeOob,
     HasNumBaseLearners,
     HasParallelism,
     HasSubBag,
 )
-from ..ensemble.utils import slice_features, subspace
+from ..ensemble.utils import OobResults, slice_features, subspace
 from ..estimator import RegressionModel, Regressor
 from ..frame import TensorFrame
 from ..parallel import get_comm
@@ -51,7 +52,7 @@ class _BaggingRegressorParams(
         return self.set("seed", v)
 
 
-class BaggingRegressor(Regressor, _BaggingRegressorParams):
+class BaggingRegressor(Regressor, _BaggingRegressorParams, HasComputeOob):
     def _default_base_learner(self):
         from ..models.tree import DecisionTreeRegressor
 
@@ -72,6 +73,8 @@ class BaggingRegressor(Regressor, _BaggingRegressorParams):
 
         from ..models.tree import DecisionTreeRegressor, fit_tree_forest
 
+        oob = self.getComputeOob()
+        inbag = None
         if (
             type(learner) is DecisionTreeRegressor
             and learner.getOrDefault("minWeightFractionPerNode") == 0.0
@@ -99,6 +102,8 @@ class BaggingRegressor(Regressor, _BaggingRegressorParams):
                 learner, f_edges, f_bins, y.unsqueeze(1), bag_w, comm,
                 subspaces=subspaces, root_rows=root_rows,
             )
+            if oob:
+                inbag = bag_w > 0
         else:
             if learner is not None and learner.hasParam("maxBins"):
                 binned.get(int(learner.getOrDefault("maxBins")))  # pre-warm
@@ -115,13 +120,17 @@ class BaggingRegressor(Regressor, _BaggingRegressorParams):
                         comm.rank,
                     )
                     fr = binned.fit_frame(learner, y, bw, subspaces[i])
-                    return self.fit_base_learner(learner, fr, weight_col="weight")
+                    fitted = self.fit_base_learner(learner, fr, weight_col="weight")
+                    return (fitted, bw > 0) if oob else fitted
                 return task
 
             from ..parallel.streams import parallel_fits
 
             models = parallel_fits([fit_one(i) for i in range(k)],
                                    self.getParallelism())
+            if oob:
+                inbag = torch.stack([b for _, b in models], dim=1)
+                models = [m for m, _ in models]
 
         model = BaggingRegressionModel()
         model._models = models
@@ -129,7 +138,51 @@ class BaggingRegressor(Regressor, _BaggingRegressorParams):
         model._num_features = num_features
         for p in ("featuresCol", "labelCol", "predictionCol"):
             model.set(p, self.getOrDefault(p))
+        if oob:
+            model._oob = self._oob_estimates(x, y, w, models, subspaces,
+                                             inbag, comm)
         return model
+
+    @staticmethod
+    def _oob_estimates(x, y, w, models, subspaces, inbag, comm):
+        """Out-of-bag predictions of the training rows and their weighted
+        R^2: member i votes on row r only where ``not inbag[r, i]``.  Tree
+        members are one ``forest_oob`` pass; anything else is a loop over
+        the members in order.  A row of instance weight 0 is out of every
+        bag: it gets a prediction and weighs nothing in the score.  The
+        score and the coverage are sums over all ranks, in float64."""
+        from ..ensemble.utils import oob_weighted_sums, packed_forest_oob
+
+        res = packed_forest_oob(x, models, subspaces, x.shape[1], inbag)
+        if res is not None:
+            sums, counts = res[0][:, 0], res[1]
+        else:
+            sums = torch.zeros(x.shape[0], dtype=torch.float32, device=x.device)
+            counts = torch.zeros(x.shape[0], dtype=torch.int32, device=x.device)
+            zero = torch.zeros((), dtype=torch.float32, device=x.device)
+            for i, (sub, m) in enumerate(zip(subspaces, models)):
+                out = ~inbag[:, i]
+                p = m.predict(slice_features(x, sub)).float()
+                sums = sums + torch.where(out, p, zero)
+                counts += out.to(torch.int32)
+        has = counts > 0
+        nan = torch.full((), float("nan"), dtype=torch.float32, device=x.device)
+        pred = torch.where(has, sums / counts, nan)
+        wc = torch.where(has, w, torch.zeros_like(w)).double()
+        yd = y.double()
+        s_all, s_w, s_wy = oob_weighted_sums(comm, [w, wc, wc * yd])
+        score = float("nan")
+        if s_w > 0:
+            mean = s_wy / s_w
+            resid = torch.where(has, yd - pred.double(), torch.zeros_like(yd))
+            ss_res, ss_tot = oob_weighted_sums(
+                comm, [wc * resid * resid, wc * (yd - mean) ** 2])
+            if ss_tot > 0:
+                score = 1.0 - ss_res / ss_tot
+        return {
+            "oobPrediction": pred, "oobCounts": counts, "oobScore": score,
+            "oobCoverage": s_w / s_all if s_all > 0 else float("nan"),
+        }
 
     # ---- fold-vectorized fitting (OOF stacking fast path) ----------------
     def _can_fit_folds(self) -> bool:
@@ -216,7 +269,8 @@ class BaggingRegressor(Regressor, _BaggingRegressorParams):
         self.setBaseLearner(self._load_learner(path))
 
 
-class BaggingRegressionModel(RegressionModel, _BaggingRegressorParams):
+class BaggingRegressionModel(RegressionModel, _BaggingRegressorParams,
+                             OobResults):
     @property
     def models(self):
         """Fitted member models (reference BaggingRegressionModel.models)."""
@@ -276,7 +330,8 @@ class BaggingRegressionModel(RegressionModel, _BaggingRegressorParams):
     def _save_impl(self, path: str):
         persistence.save_metadata(
             self, path,
-            extra={"numModels": len(self._models), "numFeatures": self._num_features},
+            extra={"numModels": len(self._models),
+                   "numFeatures": self._num_features, **self._oob_meta()},
         )
         for i, m in enumerate(self._models):
             m.save(os.path.join(path, f"model-{i}"), overwrite=True)
@@ -287,6 +342,7 @@ class BaggingRegressionModel(RegressionModel, _BaggingRegressorParams):
 
     def _load_extra(self, path: str, meta: dict):
         self._num_features = meta.get("numFeatures", -1)
+        self._load_oob(meta)
         self._models = []
         self._subspaces = []
         i = 0
