@@ -90,6 +90,17 @@ void forest_oob(torch::Tensor sums, torch::Tensor counts, torch::Tensor x,
                 torch::Tensor mask, int64_t dim, int64_t max_group_nodes);
 std::tuple<int64_t, int64_t, int64_t> forest_oob_geometry();
 
+// csrc/forest_permute.hip
+void forest_permute_loss(torch::Tensor out, torch::Tensor partials,
+                         torch::Tensor x, torch::Tensor nodes,
+                         torch::Tensor tree_off, torch::Tensor groups,
+                         torch::Tensor init, torch::Tensor label,
+                         torch::Tensor weight, torch::Tensor donor,
+                         int64_t max_group_nodes, int64_t loss_id,
+                         double param);
+std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>
+forest_permute_geometry();
+
 // csrc/linear.hip
 void logreg_loss_grad(torch::Tensor payload, torch::Tensor x, torch::Tensor y,
                       torch::Tensor w, torch::Tensor wmat, bool has_bias);

@@ -2218,6 +2218,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "out-of-bag leaf sums and counts of a packed forest under a mask");
   m.def("forest_oob_geometry", &forest_oob_geometry,
         "(threads, rows per lane, grid cap) of forest_oob");
+  m.def("forest_permute_loss", &forest_permute_loss,
+        "loss sums of a packed forest with each feature column shuffled");
+  m.def("forest_permute_geometry", &forest_permute_geometry,
+        "(threads, rows per lane, grid cap, feature chunk, group nodes, "
+        "depth cap) of forest_permute_loss");
   m.def("transpose_u8", &transpose_u8, "tiled u8 matrix transpose");
   m.def("gather_ranges", &gather_ranges,
         "one-pass concat of contiguous index ranges");

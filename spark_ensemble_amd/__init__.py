@@ -51,6 +51,9 @@ def __getattr__(name):
         "GBMRegressionModel": "spark_ensemble_amd.regression",
         "StackingRegressor": "spark_ensemble_amd.regression",
         "StackingRegressionModel": "spark_ensemble_amd.regression",
+        # model inspection
+        "PermutationImportance": "spark_ensemble_amd.inspection",
+        "permutation_importance": "spark_ensemble_amd.inspection",
     }
     if name in _public:
         import importlib

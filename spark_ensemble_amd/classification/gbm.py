@@ -669,6 +669,28 @@ class GBMClassificationModel(ProbabilisticClassificationModel, _GBMClassifierPar
             self, dataset, loss, self._dim, stages,
             lambda x: self._init.predictRaw(x)[:, : self._dim])
 
+    def permutationImportance(self, dataset: TensorFrame, numRepeats=5,
+                              seed=0, loss=None):
+        """Permutation importance on ``dataset`` (docs/importance.md): a
+        ``PermutationImportance`` with the ``[numRepeats, F]`` increases of
+        the weighted mean loss when one feature column is shuffled.
+        ``loss`` is resolved as in ``evaluateEachIteration``.  With one
+        margin column (the binary losses), built-in tree stages and a
+        constant init the whole table is one fused pass over the rows;
+        multiclass logloss and anything else is a column-swap loop over the
+        model's margins."""
+        from .. import inspection
+        from ..boosting import staged
+
+        k = self._num_classes
+        loss = staged.resolve_loss(
+            self, loss, lambda name: get_classification_loss(name, k),
+            self._dim)
+        stages = list(zip(self._models, self._weights, self._subspaces))
+        return inspection.ensemble_permutation_importance(
+            self, dataset, numRepeats, seed, loss, self._dim, stages,
+            self._init, lambda x: self._margins(x.float()))
+
     def truncate(self, n: int) -> "GBMClassificationModel":
         """A new model keeping the init and the first ``n`` stages
         (``0 <= n <= numModels``); stage models are shared, not copied."""

@@ -283,6 +283,21 @@ class DecisionTreeRegressionModel(_TreeModelMixin, RegressionModel, _TreeParams)
         every row sums to ``predict``.  NaN features are not supported."""
         return self._contrib(features.float())[:, 0, :]
 
+    def permutationImportance(self, dataset, numRepeats=5, seed=0,
+                              loss=None):
+        """Permutation importance on ``dataset`` under the squared loss
+        ``0.5 (y - predict)^2`` (docs/importance.md): a
+        ``PermutationImportance`` with the ``[numRepeats, F]`` increases of
+        the weighted mean loss when one feature column is shuffled, from
+        one fused pass over the rows.  The loss is fixed: ``loss`` must be
+        None or "squared"."""
+        from .. import inspection
+
+        return inspection.ensemble_permutation_importance(
+            self, dataset, numRepeats, seed, inspection.squared_only(loss),
+            1, [([self], [1.0], None)], None,
+            lambda x: self.predict(x).unsqueeze(1))
+
 
 def fit_tree_forest(learner, edges, bins, labels, weights, comm=None,
                     subspaces=None, root_rows=None):

@@ -1231,6 +1231,157 @@ def forest_oob(x, trees, inbag, cache=None):
     return reference.forest_oob(x, trees, inbag)
 
 
+# ---- permutation loss sums (csrc/forest_permute.hip) ----------------------
+
+# what the last forest_permute_loss call did: {"path": "native" |
+# "reference", "mode": "binned" | "raw" | None, "feature_chunk": FC,
+# "groups": G}
+last_forest_permute_info: dict = {}
+
+
+def forest_permute_geometry():
+    """(threads, rows per lane, row-tile grid cap, features per chunk, nodes
+    per LDS group, depth cap or 0) of the native ``forest_permute_loss``."""
+    return tuple(int(v) for v in
+                 _require_hip("forest_permute_loss").forest_permute_geometry())
+
+
+def _permute_groups(pack, budget):
+    """The trees of a v2 ``pack`` cut into contiguous groups of at most
+    ``budget`` nodes: ``(groups [G, 4] int32, max_nodes)`` in the layout of
+    ``pack["groups_t"]``, over the same node arena, or None when one tree
+    alone is over the budget.  ``forest_permute_loss`` shares the LDS
+    between its accumulators and the nodes, so its groups are smaller than
+    ``_FP2_GROUP_NODES``; the pack's own groups stay as the other ops read
+    them.  Cached on the pack per budget."""
+    key = ("permute_groups", int(budget))
+    if key not in pack:
+        offs = pack["offsets32"].cpu().tolist() + [int(pack["feats"].numel())]
+        sizes = [offs[t + 1] - offs[t] for t in range(pack["T"])]
+        if max(sizes) > budget:
+            pack[key] = None
+        else:
+            groups, first, acc = [], 0, 0
+            for t, s in enumerate(sizes):
+                if acc + s > budget and acc > 0:
+                    groups.append([first, t - first, offs[first], acc])
+                    first, acc = t, 0
+                acc += s
+            groups.append([first, pack["T"] - first, offs[first], acc])
+            pack[key] = (
+                torch.tensor(groups, dtype=torch.int32, device=pack["dev"]),
+                max(g[3] for g in groups))
+    return pack[key]
+
+
+def forest_permute_loss(x, trees, weights, init, label, row_weight, loss,
+                        donor, cache=None):
+    """``(base, perm)``: the weighted loss sum of a forest of scalar-leaf
+    trees on ``x`` (float64 scalar) and the same sum with column f replaced
+    by ``x[donor[r], f]`` for every repeat r and feature f (float64
+    ``[R, F]``); semantics in ``reference.forest_permute_loss``.  Both
+    results are on the device of x.
+
+    On the GPU one launch (csrc/forest_permute.hip) serves f32 rows, the
+    built-in nine losses at ``dim == 1``, forests that pack as v2 with every
+    tree within the op's own LDS group budget (``forest_permute_geometry``)
+    and ``donor`` of at most 65535 repeats; anything else runs the torch
+    reference op on the same device.  Rows are read as u8 ranks
+    (``bin_features`` against the pack's threshold sets, as
+    ``forest_predict2``) whenever the pack has them, else as f32;
+    ``SEA_PERMUTE_MODE=raw|binned`` overrides.  Both are exact.
+
+    ``cache``: caller-owned dict; the weighted pack is built once per
+    (forest, device) and kept under "pack", as ``forest_staged_loss`` keeps
+    its own.
+    """
+    N, F = x.shape
+    donor = torch.as_tensor(donor)
+    if donor.dim() != 2 or donor.shape[1] != N:
+        raise ValueError(
+            f"donor is {tuple(donor.shape)}, expected (R, {N})")
+    R = donor.shape[0]
+    if N and R and (int(donor.min()) < 0 or int(donor.max()) >= N):
+        raise ValueError(f"donor holds an index outside [0, {N})")
+    if N == 0:  # no launch, no pack
+        last_forest_permute_info.update(
+            path="reference", mode=None, feature_chunk=0, groups=0)
+        return (torch.zeros((), dtype=torch.float64, device=x.device),
+                torch.zeros(R, F, dtype=torch.float64, device=x.device))
+
+    native = (x.is_cuda and x.dtype == torch.float32 and bool(trees)
+              and 1 <= F < 32768 and N < 2 ** 31 and 1 <= R <= 65535
+              and all(t["leaf_value"].shape[1] == 1 for t in trees))
+    lp = _staged_native_loss(loss, 1) if native else None
+    m = _require_hip("forest_permute_loss") if lp is not None else None
+    if m is not None:
+        pack = cache.get("pack") if cache is not None else None
+        if (pack is None or pack["T"] != len(trees)
+                or pack["dev"] != x.device):
+            w = torch.as_tensor(
+                [float(v) for v in weights], dtype=torch.float32)
+            pack = _pack_forest(trees, w, x.device)
+            if cache is not None:
+                cache["pack"] = pack
+        threads, _, max_blocks, fc, budget, _ = (
+            int(v) for v in m.forest_permute_geometry())
+        if "f_max" not in pack:
+            pack["f_max"] = int(pack["feats"].max())
+        if pack["f_max"] >= F:
+            raise ValueError(
+                f"forest splits on feature {pack['f_max']} but x has "
+                f"{F} columns")
+        # the kernel has no depth cap (geometry's last entry is 0)
+        grp = _permute_groups(pack, budget) if pack["v2"] else None
+        if grp is not None:
+            groups, max_nodes = grp
+            binned_avail = bool(
+                pack.get("binned_ok") and pack["bin_fmax"] <= F)
+            env_mode = os.environ.get("SEA_PERMUTE_MODE")
+            mode = "raw"
+            if binned_avail and env_mode != "raw":
+                mode = "binned"
+            elif env_mode == "binned":
+                raise ValueError(
+                    "SEA_PERMUTE_MODE=binned: this forest has no u8 rank "
+                    "form (a feature with more than 255 thresholds, or no "
+                    "split at all)")
+            xc = x.contiguous()
+            if mode == "binned":
+                nodes = pack["node64b"]
+                xb = torch.empty(xc.shape, dtype=torch.uint8, device=x.device)
+                m.bin_features(xb, xc, _binned_edges(pack, F))
+                xc = xb
+            else:
+                nodes = pack["node64"]
+            C = R * F + 1
+            n_slots = min(-(-N // threads), max_blocks) * (threads // 64)
+            out = torch.empty(C, dtype=torch.float64, device=x.device)
+            partials = torch.empty(n_slots, C, dtype=torch.float64,
+                                   device=x.device)
+
+            def f32(t):
+                return t.to(x.device, torch.float32).reshape(N).contiguous()
+
+            m.forest_permute_loss(
+                out, partials, xc, nodes, pack["offsets32"], groups,
+                f32(init), f32(label), f32(row_weight),
+                donor.to(x.device, torch.int32).contiguous(),
+                int(max_nodes), int(lp[0]), float(lp[1]))
+            last_forest_permute_info.update(
+                path="native", mode=mode, feature_chunk=fc,
+                groups=int(groups.shape[0]))
+            return out[C - 1], out[:C - 1].view(R, F)
+    last_forest_permute_info.update(
+        path="reference", mode=None, feature_chunk=0, groups=0)
+    f_max = max([int(t["feature"].max()) for t in trees], default=-1)
+    if f_max >= F:
+        raise ValueError(
+            f"forest splits on feature {f_max} but x has {F} columns")
+    return reference.forest_permute_loss(
+        x, trees, weights, init, label, row_weight, loss, donor)
+
+
 def logreg_loss_grad(x, y_int, w, wmat, has_bias):
     """Single-pass fused logistic loss+gradient.
 

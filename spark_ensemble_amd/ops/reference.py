@@ -448,6 +448,65 @@ def forest_oob(x, trees, inbag):
     return sums, counts
 
 
+def forest_permute_loss(x, trees, weights, init, label, row_weight, loss,
+                        donor):
+    """Loss sums of a forest with one feature column shuffled at a time:
+    ``(base, perm)``, a float64 scalar and a float64 ``[R, F]``.
+
+    ``trees`` are T scalar-leaf trees with tree weights ``weights``,
+    ``init`` / ``label`` / ``row_weight`` are ``[N]``, ``loss`` a ``GBMLoss``
+    of ``dim == 1`` and ``donor`` ``[R, N]`` row indices, each row a
+    permutation of ``0 .. N-1``::
+
+        base       = sum_i w_i * loss(label_i, init_i + sum_t w_t leaf_t(x_i))
+        perm[r, f] = the same sum over x with column f replaced by
+                     x[donor[r], f]; every other column untouched
+
+    One permutation per repeat is shared by all features.  Routing is
+    serving's (``x <= thr`` goes left, a NaN goes right), for a donor's
+    value as for the row's own.
+
+    Runs in the dtype of ``x`` (margins and per-row weighted loss), the sum
+    over rows is always float64: ``x.double()`` gives the float64 oracle.
+    Both results are on the device of ``x``.  Naive on purpose: R * F
+    column swaps and full forest walks."""
+    dt, dev = x.dtype, x.device
+    N, F = x.shape
+    donor = torch.as_tensor(donor).to(dev, torch.long)
+    if donor.dim() != 2 or donor.shape[1] != N:
+        raise ValueError(
+            f"donor is {tuple(donor.shape)}, expected (R, {N})")
+    R = donor.shape[0]
+    if N == 0:
+        return (torch.zeros((), dtype=torch.float64, device=dev),
+                torch.zeros(R, F, dtype=torch.float64, device=dev))
+    if int(donor.min()) < 0 or int(donor.max()) >= N:
+        raise ValueError(f"donor holds an index outside [0, {N})")
+    tr = [{"feature": t["feature"].to(dev),
+           "threshold": t["threshold"].to(dev),
+           "left_child": t["left_child"].to(dev),
+           "leaf_value": t["leaf_value"].to(dev, dt)} for t in trees]
+    tw = torch.as_tensor([float(v) for v in weights], dtype=dt, device=dev)
+    ini = init.to(dev, dt).reshape(N)
+    lab = label.to(dev, dt).reshape(N, 1)
+    w = row_weight.to(dev, dt).reshape(N)
+
+    def loss_sum(xx):
+        margin = ini.clone()
+        if tr:
+            margin = margin + forest_predict(xx, tr, tw)[:, 0].to(dt)
+        return (loss.loss(lab, margin.unsqueeze(1)) * w).double().sum()
+
+    base = loss_sum(x)
+    perm = torch.empty(R, F, dtype=torch.float64, device=dev)
+    for r in range(R):
+        for f in range(F):
+            xp = x.clone()
+            xp[:, f] = x[donor[r], f]
+            perm[r, f] = loss_sum(xp)
+    return base, perm
+
+
 def logreg_loss_grad(x, y_int, w, wmat, has_bias):
     """Torch reference for the fused logistic loss+grad payload
     (dispatch.logreg_loss_grad contract)."""

@@ -327,6 +327,24 @@ class BaggingRegressionModel(RegressionModel, _BaggingRegressorParams,
             cache=self.__dict__.setdefault("_contrib_cache", {}),
         )[:, 0, :]
 
+    def permutationImportance(self, dataset, numRepeats=5, seed=0,
+                              loss=None):
+        """Permutation importance on ``dataset`` under the squared loss
+        ``0.5 (y - predict)^2`` (docs/importance.md): a
+        ``PermutationImportance`` with the ``[numRepeats, F]`` increases of
+        the weighted mean loss when one feature column is shuffled.  The
+        loss is fixed: ``loss`` must be None or "squared".  With built-in
+        tree members the whole table is one fused pass over the rows;
+        anything else is a column-swap loop over ``predict``."""
+        from .. import inspection
+
+        mcount = len(self._models)
+        stages = [([m], [1.0 / mcount], sub)
+                  for m, sub in zip(self._models, self._subspaces)]
+        return inspection.ensemble_permutation_importance(
+            self, dataset, numRepeats, seed, inspection.squared_only(loss),
+            1, stages, None, lambda x: self.predict(x).unsqueeze(1))
+
     def _save_impl(self, path: str):
         persistence.save_metadata(
             self, path,

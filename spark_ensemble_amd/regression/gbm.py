@@ -536,6 +536,27 @@ class GBMRegressionModel(RegressionModel, _GBMRegressorParams):
             self, dataset, loss, 1, stages,
             lambda x: self._init.predict(x).unsqueeze(1))
 
+    def permutationImportance(self, dataset: TensorFrame, numRepeats=5,
+                              seed=0, loss=None):
+        """Permutation importance on ``dataset`` (docs/importance.md): a
+        ``PermutationImportance`` with the ``[numRepeats, F]`` increases of
+        the weighted mean loss when one feature column is shuffled.
+        ``loss`` is resolved as in ``evaluateEachIteration``.  With built-in
+        tree stages and a constant or tree init the whole table is one
+        fused pass over the rows; anything else is a column-swap loop over
+        ``predict``."""
+        from .. import inspection
+        from ..boosting import staged
+
+        alpha = self.getOrDefault("alpha")
+        loss = staged.resolve_loss(
+            self, loss, lambda name: get_regression_loss(name, alpha=alpha), 1)
+        stages = [([m], [wt], sub) for m, wt, sub in
+                  zip(self._models, self._weights, self._subspaces)]
+        return inspection.ensemble_permutation_importance(
+            self, dataset, numRepeats, seed, loss, 1, stages, self._init,
+            lambda x: self.predict(x).unsqueeze(1))
+
     def truncate(self, n: int) -> "GBMRegressionModel":
         """A new model keeping the init and the first ``n`` stages
         (``0 <= n <= numModels``); stage models are shared, not copied."""

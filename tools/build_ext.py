@@ -24,6 +24,7 @@ SRC = [
     os.path.join(REPO, "csrc", "tree_contrib.hip"),
     os.path.join(REPO, "csrc", "forest_staged.hip"),
     os.path.join(REPO, "csrc", "forest_oob.hip"),
+    os.path.join(REPO, "csrc", "forest_permute.hip"),
 ]
 OUT = os.path.join(REPO, "spark_ensemble_amd", "_hip_ops.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
