@@ -101,6 +101,15 @@ void forest_permute_loss(torch::Tensor out, torch::Tensor partials,
 std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>
 forest_permute_geometry();
 
+// csrc/forest_wquantile.hip
+void forest_wquantile(torch::Tensor out, torch::Tensor x, torch::Tensor nodes,
+                      torch::Tensor tree_off, torch::Tensor groups,
+                      torch::Tensor qtab, torch::Tensor leaf_table,
+                      int64_t max_group_nodes);
+std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+           int64_t, int64_t>
+forest_wquantile_geometry();
+
 // csrc/linear.hip
 void logreg_loss_grad(torch::Tensor payload, torch::Tensor x, torch::Tensor y,
                       torch::Tensor w, torch::Tensor wmat, bool has_bias);

@@ -2223,6 +2223,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("forest_permute_geometry", &forest_permute_geometry,
         "(threads, rows per lane, grid cap, feature chunk, group nodes, "
         "depth cap) of forest_permute_loss");
+  m.def("forest_wquantile", &forest_wquantile,
+        "per-row weighted quantiles over the member values of a packed "
+        "forest");
+  m.def("forest_wquantile_geometry", &forest_wquantile_geometry,
+        "(rows per block, member limit) x 3, grid cap, slab bytes, group "
+        "nodes of forest_wquantile");
   m.def("transpose_u8", &transpose_u8, "tiled u8 matrix transpose");
   m.def("gather_ranges", &gather_ranges,
         "one-pass concat of contiguous index ranges");

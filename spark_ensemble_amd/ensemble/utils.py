@@ -192,6 +192,53 @@ def packed_forest_oob(x, models, subspaces, num_features, inbag, vote=None,
     return _ops.forest_oob(x, trees, inbag, cache=cache)
 
 
+def packed_forest_wquantile(x, models, weights, subspaces, num_features,
+                            probs, cache=None, native_only=False):
+    """Per-row weighted quantiles of the member predictions of an ensemble
+    of built-in regression trees as ONE ``forest_wquantile`` call:
+    ``[N, Q]``, column q the first member value, in ascending order, whose
+    cumulative weight reaches ``probs[q]`` of the total (the
+    ``weighted_median`` rule at any probability).  Subspaced members walk
+    the unsliced x through the ``_tree_orig_feats`` remap.  Returns None
+    when a member is not such a tree, and with ``native_only`` also where
+    the op would run its torch reference instead of the kernel."""
+    from ..models.tree import DecisionTreeRegressionModel
+    from ..ops import dispatch as _ops
+
+    if not models:
+        return None
+    trees = []
+    for m, sub in zip(models, subspaces):
+        if not isinstance(m, DecisionTreeRegressionModel):
+            return None
+        t = m._tree
+        feat = orig_space_features(m, sub, num_features)
+        if feat is not t["feature"]:
+            t = dict(t, feature=feat)
+        trees.append(t)
+    w = torch.tensor([float(v) for v in weights], dtype=torch.float32)
+    return _ops.forest_wquantile(x, trees, w, probs, cache=cache,
+                                 native_only=native_only)
+
+
+def member_wquantile(x, models, weights, subspaces, num_features, probs,
+                     cache=None):
+    """``packed_forest_wquantile`` for tree members; for any other member
+    the same rule over the stacked per-member predictions, in float64
+    (``reference.weighted_quantile``)."""
+    from ..ops import reference
+
+    out = packed_forest_wquantile(x, models, weights, subspaces,
+                                  num_features, probs, cache=cache)
+    if out is None:
+        preds = torch.stack(
+            [m.predict(x if sub is None else slice_features(x, sub)).float()
+             for m, sub in zip(models, subspaces)], dim=1)
+        out = reference.weighted_quantile(
+            preds, [float(v) for v in weights], probs)
+    return out
+
+
 def oob_weighted_sums(comm, terms):
     """float64 sums over the rows of every rank of each ``[N]`` tensor in
     ``terms``: one all-reduce, so every rank gets the same numbers."""

@@ -1382,6 +1382,199 @@ def forest_permute_loss(x, trees, weights, init, label, row_weight, loss,
         x, trees, weights, init, label, row_weight, loss, donor)
 
 
+# ---- weighted quantiles of member values (csrc/forest_wquantile.hip) -------
+
+WQUANTILE_MAX_MEMBERS = 256   # the member index is the low byte of a key
+WQUANTILE_MAX_PROBS = 16
+WQUANTILE_MAX_LEAF_VALUES = 1 << 24  # the value rank is the other 24 bits
+
+# what the last forest_wquantile call did: {"path": "native" | "reference",
+# "mode": "binned" | "raw" | None, "rows_per_block": R, "groups": G}
+last_forest_wquantile_info: dict = {}
+
+
+def forest_wquantile_geometry():
+    """Launch shape of the native ``forest_wquantile``: ``rows`` is
+    ``((member limit, rows per block), ...)`` in ascending member limit (the
+    padded member count picks the first limit it fits), ``max_blocks`` the
+    row-tile grid cap, ``slab_bytes`` the LDS share of the keys and
+    ``group_nodes`` the node budget of one LDS group."""
+    g = [int(v) for v in
+         _require_hip("forest_wquantile").forest_wquantile_geometry()]
+    return {"rows": ((g[1], g[0]), (g[3], g[2]), (g[5], g[4])),
+            "max_blocks": g[6], "slab_bytes": g[7], "group_nodes": g[8]}
+
+
+def _wquantile_ranks(pack):
+    """Leaf-rank arenas of a unit-weight D == 1 v2 ``pack``, cached on it:
+    ``leaf_table`` [U] f32, the sorted distinct leaf values of the whole
+    forest (-0.0 and +0.0 are one value), and ``node64r`` / ``node64rb``,
+    copies of ``node64`` / ``node64b`` whose LEAF payload is the rank of
+    the leaf's value in that table (inner nodes unchanged), as
+    ``_pack_forest_binned`` puts threshold ranks into inner payloads.  None
+    when a leaf is NaN (a NaN has no rank) or U exceeds 24 bits."""
+    if "wq_ranks" not in pack:
+        leaf = pack["feats"] < 0
+        vals = pack["leaves"][leaf, 0] + 0.0  # -0.0 + 0.0 = +0.0
+        ranks = None
+        if not bool(torch.isnan(vals).any()):
+            table, inv = torch.unique(vals, return_inverse=True)
+            if table.numel() <= WQUANTILE_MAX_LEAF_VALUES:
+                rank_full = torch.zeros_like(pack["node64"])
+                rank_full[leaf] = inv
+
+                def with_ranks(arena):
+                    return torch.where(
+                        leaf, (arena & 0xFFFFFFFF) | (rank_full << 32),
+                        arena).contiguous()
+
+                ranks = {"leaf_table": table.contiguous(),
+                         "node64r": with_ranks(pack["node64"])}
+                if pack.get("binned_ok"):
+                    ranks["node64rb"] = with_ranks(pack["node64b"])
+        pack["wq_ranks"] = ranks
+    return pack["wq_ranks"]
+
+
+def _wquantile_qtab(weights, probs):
+    """Exact integer form of the rule ``cum >= p * total``: the f32 member
+    weights scaled by one power of two into integers q_t, and per
+    probability the threshold ``ceil(p * sum q_t)`` from exact rationals, so
+    ``cum_q >= threshold`` decides what the real numbers decide.  Returns the
+    ``M + Q`` integers, or None when a weight is not finite or the scaled
+    sums could leave 62 bits."""
+    from fractions import Fraction
+
+    w32 = torch.as_tensor(weights, dtype=torch.float32).reshape(-1)
+    if not bool(torch.isfinite(w32).all()):
+        return None
+    fr = [Fraction(v) for v in w32.tolist()]
+    den = max(f.denominator for f in fr)  # denominators are powers of two
+    q = [int(f * den) for f in fr]
+    if len(q) * max(abs(v) for v in q) >= 1 << 62:
+        return None
+    total = sum(q)
+    # ceil(a / b) == -((-a) // b) for b > 0
+    thr = []
+    for p in probs:
+        t = Fraction(p) * total
+        thr.append(-((-t.numerator) // t.denominator))
+    return q + thr
+
+
+def forest_wquantile(x, trees, weights, probs, cache=None,
+                     native_only=False):
+    """Per-row weighted quantiles over the member values of a forest of
+    scalar-leaf trees: ``[N, Q]`` f32 on the device of x, ``out[i, q]`` the
+    first of the M values ``leaf_t(x_i)``, in ascending order, whose
+    cumulative member weight reaches ``probs[q]`` times the total weight
+    (the smallest value when none does); semantics in
+    ``reference.forest_wquantile``.  ``weights`` are read as f32.
+
+    On the GPU one launch (csrc/forest_wquantile.hip) walks the forest,
+    orders each row's member values on chip and selects in exact integer
+    arithmetic.  It serves f32 rows, ``1 <= M <= 256`` trees with ``D == 1``
+    that pack as v2 with every tree within the op's LDS group budget
+    (``forest_wquantile_geometry``), no NaN leaf, at most 2^24 distinct leaf
+    values, ``1 <= Q <= 16`` and weights that scale to integers within 62
+    bits; anything else runs the torch reference op on the same device.
+    Rows are read as u8 ranks (``bin_features`` against the pack's threshold
+    sets, as ``forest_predict2``) whenever the pack has them, else as f32;
+    ``SEA_WQUANTILE_MODE=raw|binned`` overrides.  Both are exact.
+    ``native_only``: return None where the reference op would run, for a
+    caller that has a route of its own for those cases.
+
+    The kernel decides ``cum >= p * total`` in exact arithmetic, the
+    reference op in float64 with ``p * total`` rounded.  They agree whenever
+    the float64 sums and that product are exact (weights and p with few
+    significant bits, as in every test); otherwise they can differ on a row
+    whose cumulative weight lies within a float64 rounding of the
+    threshold.
+
+    ``cache``: caller-owned dict; the pack (tree weights all 1.0) is built
+    once per (forest, device) and kept under "pack".  Keep a dict of its own
+    for this op, for the reason ``forest_oob`` gives.
+    """
+    if not trees:
+        raise ValueError("forest_wquantile needs at least one tree")
+    probs = [float(p) for p in probs]
+    if not all(0.0 <= p <= 1.0 for p in probs):
+        raise ValueError(f"probabilities must lie in [0, 1], got {probs}")
+    N, F = x.shape
+    M, Q = len(trees), len(probs)
+    w32 = torch.as_tensor(weights, dtype=torch.float32).reshape(-1)
+    if w32.numel() != M:
+        raise ValueError(f"{w32.numel()} weights for {M} trees")
+
+    def check_features(f_max):
+        if f_max >= F:
+            raise ValueError(
+                f"forest splits on feature {f_max} but x has {F} columns")
+
+    # N == 0 launches nothing and packs nothing
+    native = (x.is_cuda and x.dtype == torch.float32 and 1 <= F < 32768
+              and N >= 1
+              and 1 <= M <= WQUANTILE_MAX_MEMBERS
+              and 1 <= Q <= WQUANTILE_MAX_PROBS
+              and all(t["leaf_value"].shape[1] == 1 for t in trees))
+    qtab = _wquantile_qtab(w32, probs) if native else None
+    m = _require_hip("forest_wquantile") if qtab is not None else None
+    if m is not None:
+        pack = cache.get("pack") if cache is not None else None
+        fits = (pack is not None and pack["T"] == M
+                and pack["dev"] == x.device)
+        if not (fits and pack.get("unit_weights")):
+            pack = _pack_forest(trees, None, x.device)
+            pack["unit_weights"] = True
+            if cache is not None and not fits:
+                cache["pack"] = pack
+        if "f_max" not in pack:
+            pack["f_max"] = int(pack["feats"].max())
+        check_features(pack["f_max"])
+        geo = forest_wquantile_geometry()
+        grp = _permute_groups(pack, geo["group_nodes"]) if pack["v2"] else None
+        ranks = _wquantile_ranks(pack) if grp is not None else None
+        if ranks is not None:
+            groups, max_nodes = grp
+            binned_avail = bool("node64rb" in ranks and pack["bin_fmax"] <= F)
+            env_mode = os.environ.get("SEA_WQUANTILE_MODE")
+            mode = "raw"
+            if binned_avail and env_mode != "raw":
+                mode = "binned"
+            elif env_mode == "binned":
+                raise ValueError(
+                    "SEA_WQUANTILE_MODE=binned: this forest has no u8 rank "
+                    "form (a feature with more than 255 thresholds, or no "
+                    "split at all)")
+            xc = x.contiguous()
+            if mode == "binned":
+                nodes = ranks["node64rb"]
+                xb = torch.empty(xc.shape, dtype=torch.uint8, device=x.device)
+                m.bin_features(xb, xc, _binned_edges(pack, F))
+                xc = xb
+            else:
+                nodes = ranks["node64r"]
+            m_pad = 1 << (M - 1).bit_length()
+            rows = next(r for lim, r in geo["rows"] if m_pad <= lim)
+            out = torch.empty(N, Q, dtype=torch.float32, device=x.device)
+            m.forest_wquantile(
+                out, xc, nodes, pack["offsets32"], groups,
+                torch.tensor(qtab, dtype=torch.int64).to(x.device),
+                ranks["leaf_table"], int(max_nodes))
+            last_forest_wquantile_info.update(
+                path="native", mode=mode, rows_per_block=rows,
+                groups=int(groups.shape[0]))
+            return out
+    last_forest_wquantile_info.update(
+        path="reference", mode=None, rows_per_block=0, groups=0)
+    if native_only:
+        return None
+    check_features(max(int(t["feature"].max()) for t in trees))
+    if N == 0:
+        return torch.empty(0, Q, dtype=torch.float32, device=x.device)
+    return reference.forest_wquantile(x, trees, w32, probs)
+
+
 def logreg_loss_grad(x, y_int, w, wmat, has_bias):
     """Single-pass fused logistic loss+gradient.
 

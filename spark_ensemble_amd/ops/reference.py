@@ -507,6 +507,53 @@ def forest_permute_loss(x, trees, weights, init, label, row_weight, loss,
     return base, perm
 
 
+def weighted_quantile(values, weights, probs):
+    """Row-wise weighted quantiles of ``values`` ``[N, M]`` under the member
+    weights ``weights`` ``[M]``: ``[N, Q]`` in the dtype of ``values``.
+
+    The rule of ``ensemble.utils.weighted_median`` (reference
+    Utils.scala:26-40) at any probability: sort a row's M values ascending
+    (stable: equal values keep member order), take the first whose
+    cumulative weight ``>= p * total weight``; if none reaches it (negative
+    weights), take the first sorted value.  The weights are read as f32 and
+    every sum, and ``p * total``, is float64: exact for dyadic weights and
+    probabilities, rounded otherwise (the integer kernel behind
+    ``dispatch.forest_wquantile`` never rounds, so the two can differ on a
+    row whose cumulative weight is within one rounding of the threshold)."""
+    probs = [float(p) for p in probs]
+    if not all(0.0 <= p <= 1.0 for p in probs):
+        raise ValueError(f"probabilities must lie in [0, 1], got {probs}")
+    w = torch.as_tensor(weights, dtype=torch.float32).to(values.device)
+    w = w.reshape(-1).double()
+    order = values.argsort(dim=1, stable=True)
+    v_sorted = values.gather(1, order)
+    cum = w[order].cumsum(dim=1)
+    total = w.sum()
+    out = torch.empty(values.shape[0], len(probs), dtype=values.dtype,
+                      device=values.device)
+    for q, p in enumerate(probs):
+        # argmax of an all-False row is 0: the first sorted value
+        idx = (cum >= p * total).to(torch.uint8).argmax(dim=1, keepdim=True)
+        out[:, q] = v_sorted.gather(1, idx).squeeze(1)
+    return out
+
+
+def forest_wquantile(x, trees, weights, probs):
+    """Weighted quantiles over the member values of a forest of scalar-leaf
+    trees: ``out[i, q]`` is ``weighted_quantile`` of the M values
+    ``leaf_t(x_i)`` under ``weights`` at ``probs[q]``, ``[N, Q]`` on the
+    device of ``x``.  Routing is serving's (``x <= thr`` goes left, a NaN
+    goes right)."""
+    if not trees:
+        raise ValueError("forest_wquantile needs at least one tree")
+    vals = torch.stack([
+        tree_predict(
+            x, *(tree[k].to(x.device) for k in
+                 ("feature", "threshold", "left_child", "leaf_value")), 64,
+        )[:, 0] for tree in trees], dim=1)
+    return weighted_quantile(vals, weights, probs)
+
+
 def logreg_loss_grad(x, y_int, w, wmat, has_bias):
     """Torch reference for the fused logistic loss+grad payload
     (dispatch.logreg_loss_grad contract)."""

@@ -312,6 +312,21 @@ class BaggingRegressionModel(RegressionModel, _BaggingRegressorParams,
             acc = p if acc is None else acc + p
         return acc / mcount
 
+    def predictQuantile(self, features: torch.Tensor,
+                        probabilities) -> torch.Tensor:
+        """Per-row quantiles of the member predictions, every member
+        weighing the same: ``[N, Q]``, column q the first member value, in
+        ascending order, with at least ``probabilities[q]`` of the members
+        at or below it (docs/bagging.md).  A member predicts on its own
+        subspace.  Raises ValueError for a probability outside [0, 1]."""
+        from ..ensemble.utils import member_wquantile
+
+        x = features.float()
+        return member_wquantile(
+            x, self._models, [1.0] * len(self._models), self._subspaces,
+            x.shape[1], probabilities,
+            cache=self.__dict__.setdefault("_wquantile_cache", {}))
+
     def predictContrib(self, features: torch.Tensor) -> torch.Tensor:
         """Per-row additive feature contributions ``[N, F + 1]`` in the
         original feature space (path-dependent TreeSHAP,

@@ -31,7 +31,11 @@ from ..ensemble.params import (
     HasCheckpointInterval,
     HasNumBaseLearners,
 )
-from ..ensemble.utils import weighted_median
+from ..ensemble.utils import (
+    member_wquantile,
+    packed_forest_wquantile,
+    weighted_median,
+)
 from ..estimator import RegressionModel, Regressor
 from ..frame import TensorFrame
 from ..params import ParamValidators
@@ -197,11 +201,35 @@ class BoostingRegressionModel(RegressionModel, _BoostingRegressorParams):
 
     def predict(self, features: torch.Tensor) -> torch.Tensor:
         x = features.float()
+        if x.is_cuda and self.getVotingStrategy() == "median":
+            # tree members: walk, order and select in one forest_wquantile
+            # launch, the rule decided in exact arithmetic (docs/boosting.md);
+            # what the kernel does not serve keeps the route below
+            packed = packed_forest_wquantile(
+                x, self._models, self._weights, [None] * len(self._models),
+                x.shape[1], [0.5], native_only=True,
+                cache=self.__dict__.setdefault("_wquantile_cache", {}))
+            if packed is not None:
+                return packed[:, 0]
         preds = torch.stack([m.predict(x) for m in self._models], dim=1)  # [N, M]
         wts = torch.tensor(self._weights, dtype=torch.float32, device=x.device)
         if self.getVotingStrategy() == "median":
             return weighted_median(preds, wts.unsqueeze(0).expand_as(preds))
         return (preds * wts).sum(dim=1) / wts.sum()
+
+    def predictQuantile(self, features: torch.Tensor,
+                        probabilities) -> torch.Tensor:
+        """Per-row weighted quantiles of the stage predictions under the
+        stage weights: ``[N, Q]``, column q the first stage value, in
+        ascending order, whose cumulative weight reaches
+        ``probabilities[q]`` of the total weight (docs/boosting.md).
+        ``[0.5]`` is the rule of median voting.  Raises ValueError for a
+        probability outside [0, 1]."""
+        x = features.float()
+        return member_wquantile(
+            x, self._models, self._weights, [None] * len(self._models),
+            x.shape[1], probabilities,
+            cache=self.__dict__.setdefault("_wquantile_cache", {}))
 
     def _save_impl(self, path: str):
         persistence.save_metadata(
