@@ -17,6 +17,14 @@
 // rate, not a missing opcode) — so the speed-of-light design is a
 // single-pass vector kernel at HBM rate, which this is.
 //
+// That argument holds for the shapes this kernel takes (K <= 8 inside the
+// register cap of logreg_fused_supported).  Everything else up to K = 32 and
+// F = 1024 goes to csrc/linear_wide.hip, which does use the matrix pipe
+// (v_mfma_f32_16x16x4f32), for its data layout and register economy rather
+// than a higher peak; "no MFMA in csrc/" is no longer true.
+// The dispatcher also prefers it above 512 features where both kernels take
+// the shape: it measured 1.6x to 3.1x faster there (profiles/logreg_wide.md).
+//
 // Work layout per wave (64 lanes):
 //   lane l owns features {j*256 + l*4 .. +3} for j < n_chunks (dwordx4
 //   coalesced loads of X rows), W lives transposed in LDS ([K][F], lane

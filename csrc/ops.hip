@@ -2188,6 +2188,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("logreg_loss_grad", &logreg_loss_grad,
         "single-pass fused logistic loss+gradient");
   m.def("logreg_fused_supported", &logreg_fused_supported);
+  m.def("logreg_loss_grad_wide", &logreg_loss_grad_wide,
+        "fused logistic loss+gradient on f32 MFMA tiles, K <= 32, F <= 1024");
+  m.def("logreg_wide_supported", &logreg_wide_supported);
+  m.def("logreg_wide_geometry", &logreg_wide_geometry,
+        "(padded classes, feature slices, rows per block tile, LDS bytes) of "
+        "logreg_loss_grad_wide");
   m.def("split_argmax", &split_argmax,
         "fused best-split gain scan + argmax over node histograms");
   m.def("sample_weights", &sample_weights, "counter-based Poisson/Bernoulli row weights");

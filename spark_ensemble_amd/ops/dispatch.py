@@ -1575,25 +1575,46 @@ def forest_wquantile(x, trees, weights, probs, cache=None,
     return reference.forest_wquantile(x, trees, w32, probs)
 
 
-def logreg_loss_grad(x, y_int, w, wmat, has_bias):
+def logreg_loss_grad(x, y_int, w, wmat, has_bias, native_only=False):
     """Single-pass fused logistic loss+gradient.
 
     Returns payload [1 + (F+1)*K]: [loss_sum, grad(F,K) flat, grad_bias(K)]
     (unnormalized sums; caller all-reduces and divides by total weight).
-    On GPU uses the hand-written gfx950 kernel (csrc/linear.hip) when the
-    (F, K) shape fits the register budget, else the torch fallback.
+    On GPU uses the hand-written gfx950 kernels: the narrow vector kernel
+    (csrc/linear.hip) where the (F, K) shape fits its register budget, else
+    the MFMA kernel (csrc/linear_wide.hip) for K <= 32 and F <= 1024, else
+    the torch fallback.  Where both kernels take the shape and F > 512 the
+    MFMA kernel runs: at 768 and 1024 features it measured 1.6x to 3.1x
+    faster than the narrow one for K = 2..5 (profiles/logreg_wide.md) and it
+    is bitwise reproducible, which the narrow kernel's f32 atomics are not.
+
+    ``native_only``: return None where the torch fallback would run.
     """
     f = x.shape[1]
     k = wmat.shape[1]
     if x.is_cuda:
         m = _require_hip("logreg_loss_grad")
-        if m is not None and m.logreg_fused_supported(f, k):
-            payload = torch.zeros(
-                1 + (f + 1) * k, dtype=torch.float32, device=x.device
-            )
-            m.logreg_loss_grad(
-                payload, x.contiguous(), y_int.contiguous(),
-                w.contiguous(), wmat.contiguous(), bool(has_bias),
-            )
-            return payload
+        if m is not None:
+            wide = x.shape[0] > 0 and m.logreg_wide_supported(f, k)
+            if m.logreg_fused_supported(f, k) and not (wide and f > 512):
+                payload = torch.zeros(
+                    1 + (f + 1) * k, dtype=torch.float32, device=x.device
+                )
+                kernel = m.logreg_loss_grad
+            elif wide:
+                # every entry is written by the slot reduction
+                payload = torch.empty(
+                    1 + (f + 1) * k, dtype=torch.float32, device=x.device
+                )
+                kernel = m.logreg_loss_grad_wide
+            else:
+                kernel = None
+            if kernel is not None:
+                kernel(
+                    payload, x.contiguous(), y_int.contiguous(),
+                    w.contiguous(), wmat.contiguous(), bool(has_bias),
+                )
+                return payload
+    if native_only:
+        return None
     return reference.logreg_loss_grad(x, y_int, w, wmat, has_bias)

@@ -21,6 +21,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = [
     os.path.join(REPO, "csrc", "ops.hip"),
     os.path.join(REPO, "csrc", "linear.hip"),
+    os.path.join(REPO, "csrc", "linear_wide.hip"),
     os.path.join(REPO, "csrc", "wide_class.hip"),
     os.path.join(REPO, "csrc", "tree_contrib.hip"),
     os.path.join(REPO, "csrc", "forest_staged.hip"),
@@ -38,9 +39,12 @@ SRC = [
 # same results, and the guarded build times level with the other up to 50
 # members and 0.8 % slower at 200 (55.79 against 55.33 ms;
 # profiles/wquantile.md).
+# linear_wide.hip: the same guard; its f32 arithmetic is MFMA plus a scalar
+# softmax, so nothing in it wants the packed forms.
+_NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SRC_FLAGS = {
-    "forest_wquantile.hip": [
-        "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "forest_wquantile.hip": _NO_PACKED_F32,
+    "linear_wide.hip": _NO_PACKED_F32,
 }
 OUT = os.path.join(REPO, "spark_ensemble_amd", "_hip_ops.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")

@@ -56,9 +56,80 @@ def arm():
     }))
 
 
+WIDE_SHAPES = [(2_000_000, 1024, 3), (5_000_000, 256, 26),
+               (1_000_000, 1024, 32), (20_000, 16, 26)]
+
+
+# shapes the narrow kernel serves too, for the dispatcher's choice between
+# the two native kernels
+BOTH_SHAPES = [(2_000_000, 1024, 2), (2_000_000, 1024, 4),
+               (2_000_000, 768, 3), (2_000_000, 768, 5),
+               (2_000_000, 512, 3), (2_000_000, 512, 8),
+               (4_000_000, 256, 3), (4_000_000, 256, 8)]
+
+
+def wide(reps=7, shapes=None):
+    """The MFMA kernel (csrc/linear_wide.hip) against the three-pass torch
+    path it replaces, and against the narrow kernel where that one serves the
+    shape: same process, arms alternating, after warm-up, each call timed on
+    the host around a device synchronise.  One JSON line per shape with the
+    median and the min..max spread in ms and bytes/s as N*F*4 / median."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from spark_ensemble_amd.ops import dispatch, reference
+
+    m = dispatch._load_hip()
+    dev = "cuda:0"
+    for n, F, K in shapes or WIDE_SHAPES:
+        g = torch.Generator(device=dev).manual_seed(1)
+        x = torch.randn(n, F, generator=g, device=dev)
+        y = torch.randint(0, K, (n,), generator=g, device=dev, dtype=torch.int32)
+        w = torch.rand(n, generator=g, device=dev)
+        wmat = 0.05 * torch.randn(F + 1, K, generator=g, device=dev)
+
+        def native(fn, zero):
+            def call():
+                make = torch.zeros if zero else torch.empty
+                payload = make(1 + (F + 1) * K, dtype=torch.float32, device=dev)
+                fn(payload, x, y, w, wmat, True)
+                return payload
+            return call
+
+        arms = {"wide": native(m.logreg_loss_grad_wide, False),
+                "torch": lambda: reference.logreg_loss_grad(x, y, w, wmat, True)}
+        if m.logreg_fused_supported(F, K):
+            arms["narrow"] = native(m.logreg_loss_grad, True)
+        out = {name: call() for name, call in arms.items()}  # warm-up
+        torch.cuda.synchronize()
+        times = {name: [] for name in arms}
+        for _ in range(reps):
+            for name, call in arms.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                call()
+                torch.cuda.synchronize()
+                times[name].append((time.perf_counter() - t0) * 1e3)
+        row = {"n": n, "F": F, "K": K,
+               "geometry": list(m.logreg_wide_geometry(F, K))}
+        for name, ts in times.items():
+            ts.sort()
+            med = ts[len(ts) // 2]
+            row[name] = {"ms": round(med, 3), "min": round(ts[0], 3),
+                         "max": round(ts[-1], 3),
+                         "tb_per_s": round(n * F * 4 / med / 1e9, 3)}
+            ref = out["torch"]
+            row[name]["max_rel_vs_torch"] = float(
+                (out[name] - ref).abs().max() / ref.abs().max())
+        print(json.dumps(row), flush=True)
+        del x, out
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "arm":
         arm()
+    elif len(sys.argv) > 1 and sys.argv[1] == "wide":
+        wide()
+    elif len(sys.argv) > 1 and sys.argv[1] == "both":
+        wide(shapes=BOTH_SHAPES)
     else:
         arms = {
             "rr2_lds": {},
