@@ -2194,6 +2194,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("logreg_wide_geometry", &logreg_wide_geometry,
         "(padded classes, feature slices, rows per block tile, LDS bytes) of "
         "logreg_loss_grad_wide");
+  m.def("linear_gram", &linear_gram,
+        "weighted Gram matrix of [x, 1, y] in f64 on f32 MFMA tiles, "
+        "F + 2 <= 1024");
+  m.def("linear_gram_supported", &linear_gram_supported);
+  m.def("linear_gram_geometry", &linear_gram_geometry,
+        "(column tiles, panels, rows per tile, LDS bytes, rows between f32 "
+        "flushes, largest single-panel F) of linear_gram");
   m.def("split_argmax", &split_argmax,
         "fused best-split gain scan + argmax over node histograms");
   m.def("sample_weights", &sample_weights, "counter-based Poisson/Bernoulli row weights");

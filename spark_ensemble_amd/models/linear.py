@@ -76,18 +76,31 @@ class LinearRegression(Regressor, _LinearParams):
         x, y, w = self._extract_xyw(dataset)
         comm = get_comm()
         intercept = self.getOrDefault("fitIntercept")
-        if intercept:
-            ones = torch.ones(x.shape[0], 1, dtype=x.dtype, device=x.device)
-            xa = torch.cat([x, ones], dim=1)
+        if x.is_cuda:
+            # one fused pass over X (HIP kernel csrc/linear_gram.hip): the f64
+            # Gram matrix of [x, 1, y] holds both sides of the normal equations
+            from ..ops import dispatch
+
+            g = dispatch.weighted_gram(x, y, w)
+            if comm.is_distributed:
+                comm.all_reduce_(g)
+            nx = x.shape[1]
+            f = nx + 1 if intercept else nx
+            gram = g[:f, :f]
+            rhs = g[:f, nx + 1]
         else:
-            xa = x
-        f = xa.shape[1]
-        xw = xa * w.unsqueeze(1)
-        gram = xw.T @ xa  # [F, F]
-        rhs = xw.T @ y  # [F]
-        if comm.is_distributed:
-            comm.all_reduce_(gram)
-            comm.all_reduce_(rhs)
+            if intercept:
+                ones = torch.ones(x.shape[0], 1, dtype=x.dtype, device=x.device)
+                xa = torch.cat([x, ones], dim=1)
+            else:
+                xa = x
+            f = xa.shape[1]
+            xw = xa * w.unsqueeze(1)
+            gram = xw.T @ xa  # [F, F]
+            rhs = xw.T @ y  # [F]
+            if comm.is_distributed:
+                comm.all_reduce_(gram)
+                comm.all_reduce_(rhs)
         lam = self.getOrDefault("regParam")
         reg = torch.eye(f, dtype=gram.dtype, device=gram.device) * (lam + 1e-8)
         if intercept:

@@ -1618,3 +1618,40 @@ def logreg_loss_grad(x, y_int, w, wmat, has_bias, native_only=False):
     if native_only:
         return None
     return reference.logreg_loss_grad(x, y_int, w, wmat, has_bias)
+
+
+last_weighted_gram_info: dict = {}
+
+
+def weighted_gram(x, y, w, native_only=False):
+    """Augmented weighted Gram matrix ``G = sum_i w_i z_i z_i^T``,
+    ``z_i = [x_i, 1, y_i]``, ``[F+2, F+2]``: ``G[:F+1, :F+1]`` is
+    ``X_a^T W X_a`` and ``G[:F+1, F+1]`` is ``X_a^T W y``.
+
+    On GPU, for f32 inputs with ``F + 2 <= 1024`` and at least one row, the
+    MFMA kernel (csrc/linear_gram.hip) runs: one pass over x, f64 result,
+    exactly symmetric and bitwise reproducible.  Every supported shape takes
+    it; the measured times against the two-GEMM path it replaces are in
+    profiles/linear_gram.md.  Otherwise reference.weighted_gram runs in the
+    dtype of the inputs.
+
+    ``native_only``: return None where the reference would run.
+    """
+    f = x.shape[1]
+    if x.is_cuda and x.dtype == torch.float32:
+        m = _require_hip("weighted_gram")
+        if m is not None and x.shape[0] > 0 and m.linear_gram_supported(f):
+            g = torch.empty(f + 2, f + 2, dtype=torch.float64, device=x.device)
+            m.linear_gram(g, x.contiguous(), y.float().contiguous(),
+                          w.float().contiguous())
+            tiles, panels, rows, lds, flush, _ = m.linear_gram_geometry(f)
+            last_weighted_gram_info.update(
+                path="native", tiles=tiles, panels=panels, rows_per_tile=rows,
+                lds_bytes=lds, flush_rows=flush)
+            return g
+    last_weighted_gram_info.update(
+        path="reference", tiles=0, panels=0, rows_per_tile=0, lds_bytes=0,
+        flush_rows=0)
+    if native_only:
+        return None
+    return reference.weighted_gram(x, y, w)

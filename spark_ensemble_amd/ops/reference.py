@@ -554,6 +554,15 @@ def forest_wquantile(x, trees, weights, probs):
     return weighted_quantile(vals, weights, probs)
 
 
+def weighted_gram(x, y, w):
+    """Augmented weighted Gram matrix ``sum_i w_i z_i z_i^T`` with
+    ``z_i = [x_i, 1, y_i]``, ``[F+2, F+2]`` in the dtype of the inputs
+    (dispatch.weighted_gram contract).  The weight scales one operand only,
+    so zero and negative weights follow the formula."""
+    z = torch.cat([x, torch.ones_like(y).unsqueeze(1), y.unsqueeze(1)], dim=1)
+    return (z * w.unsqueeze(1)).T @ z
+
+
 def logreg_loss_grad(x, y_int, w, wmat, has_bias):
     """Torch reference for the fused logistic loss+grad payload
     (dispatch.logreg_loss_grad contract)."""

@@ -22,6 +22,7 @@ SRC = [
     os.path.join(REPO, "csrc", "ops.hip"),
     os.path.join(REPO, "csrc", "linear.hip"),
     os.path.join(REPO, "csrc", "linear_wide.hip"),
+    os.path.join(REPO, "csrc", "linear_gram.hip"),
     os.path.join(REPO, "csrc", "wide_class.hip"),
     os.path.join(REPO, "csrc", "tree_contrib.hip"),
     os.path.join(REPO, "csrc", "forest_staged.hip"),
@@ -41,10 +42,13 @@ SRC = [
 # profiles/wquantile.md).
 # linear_wide.hip: the same guard; its f32 arithmetic is MFMA plus a scalar
 # softmax, so nothing in it wants the packed forms.
+# linear_gram.hip: the same guard; its f32 arithmetic is MFMA plus one scalar
+# multiply by the row weight per fragment.
 _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SRC_FLAGS = {
     "forest_wquantile.hip": _NO_PACKED_F32,
     "linear_wide.hip": _NO_PACKED_F32,
+    "linear_gram.hip": _NO_PACKED_F32,
 }
 OUT = os.path.join(REPO, "spark_ensemble_amd", "_hip_ops.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
