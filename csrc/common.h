@@ -110,6 +110,13 @@ std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
            int64_t, int64_t>
 forest_wquantile_geometry();
 
+// csrc/gbm_round.hip
+void gbm_round_prologue(torch::Tensor gh, torch::Tensor grad,
+                        torch::Tensor gmax, torch::Tensor label,
+                        torch::Tensor pred, torch::Tensor weight,
+                        int64_t loss_id, double param, bool unit_weight);
+std::tuple<int64_t, int64_t> gbm_round_prologue_geometry(int64_t n);
+
 // csrc/linear.hip
 void logreg_loss_grad(torch::Tensor payload, torch::Tensor x, torch::Tensor y,
                       torch::Tensor w, torch::Tensor wmat, bool has_bias);

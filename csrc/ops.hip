@@ -2248,6 +2248,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("leaf_scatter", &leaf_scatter,
         "scatter per-segment leaf values into the [N, T] train-pred matrix");
   m.def("grad_hess", &grad_hess, "fused per-row loss gradient/hessian");
+  m.def("gbm_round_prologue", &gbm_round_prologue,
+        "dim-1 GBM round: weighted negative gradient, gh matrix, max |grad|");
+  m.def("gbm_round_prologue_geometry", &gbm_round_prologue_geometry,
+        "(threads per block, blocks) of gbm_round_prologue at n rows");
   m.def("line_search_eval", &line_search_eval, "fused loss+grad line-search payload");
   m.def("newton_chain_1d", &newton_chain_1d,
         "device-chained safeguarded-Newton stage-weight search");

@@ -76,6 +76,41 @@ class GBMParams(
             seed=0,
         )
 
+    def _fused_round_wstats(self, learner, dim, idx, x, w, comm, state):
+        """The per-fit weight statistics when this round may run through
+        ``models.tree.fit_gbm_round_tree`` (one native pass from the margins
+        to the grower's gradient matrix), else None: one margin column,
+        gradient updates, full bags, the identity subspace, the built-in
+        regression tree without a weight-fraction threshold, GPU tensors with
+        the HIP extension, no zero weight, and ``SEA_ROUND_FUSED`` not "0"
+        (read at every call).  ``state`` is fit-local and caches the
+        statistics, taken with one host sync on the first eligible round: the
+        weights of a full bag are the same in every round."""
+        from ..ensemble.binning import _is_identity
+        from ..models.tree import DecisionTreeRegressor, fit_weight_stats
+        from ..ops import dispatch as ops
+
+        if "static_ok" not in state:
+            state["static_ok"] = (
+                type(learner) is DecisionTreeRegressor
+                and learner.getOrDefault("minWeightFractionPerNode") == 0.0
+            )
+        if not (
+            dim == 1
+            and state["static_ok"]
+            and self.getOrDefault("updates") == "gradient"
+            and self.getSubsampleRatio() >= 1.0
+            and not self.getReplacement()
+            and x.is_cuda
+            and ops.round_fused_enabled()
+            and ops.hip_available()
+            and _is_identity(idx, x.shape[1])
+        ):
+            return None
+        if state.get("wstats") is None:
+            state["wstats"] = fit_weight_stats(w, comm)
+        return None if state["wstats"]["has_zero"] else state["wstats"]
+
     def setOptimizedWeights(self, v):
         return self.set("optimizedWeights", v)
 

@@ -212,65 +212,81 @@ class GBMClassifier(ProbabilisticClassifier, _GBMClassifierParams):
             idx = subspaces[i]
             xs = binned.sliced_features(idx)
 
-            bag_m = self.sample_weights(
-                self.getReplacement(),
-                self.getSubsampleRatio(),
-                n,
-                seed + i,
-                device,
-                None,
-                comm.rank,
-            )
-            bag_w = bag_m * w
-
-            newton = use_newton and loss.has_hessian
-            g, h = loss.grad_hess_fused(ylab, predictions, want_hess=newton)
-            if newton:
-                h = h.clamp_min(1e-2)  # [N, dim]
-                sum_h = (h * bag_m.unsqueeze(1)).sum(dim=0)
-                comm.all_reduce_(sum_h)
-                res_label = -g / h  # [N, dim]
-                res_weight = 0.5 * h / sum_h.unsqueeze(0) * bag_w.unsqueeze(1)
-            else:
-                res_label = -g
-                res_weight = bag_w.unsqueeze(1).expand(-1, dim)
-
-            # K per-class base-regressor fits.  The reference runs these
-            # as driver-side parallel futures (:377-411); here, when the
-            # base learner is the built-in histogram tree, ALL K trees
-            # grow level-synchronously in fused kernel launches (ONE
-            # histogram build + ONE all-reduce per level for the whole
-            # round — tree_grower.grow_forest).  Generic base learners
-            # keep the sequential per-class path.
+            # one margin column on full bags: the round's base fit runs from
+            # the margins in one native pass (fit_gbm_round_tree); the bag
+            # multiplicities are exactly 1, so the bag weights are ``w``
             directions = None
-            if dim > 1 and self._can_fuse_round(learner, res_weight,
-                                                fuse_state):
-                from ..models.tree import fit_tree_forest
+            wstats = self._fused_round_wstats(
+                learner, dim, idx, x, w, comm, fuse_state)
+            if wstats is not None:
+                from ..models.tree import fit_gbm_round_tree
 
-                f_edges, f_bins = binned.sliced_binned(
-                    idx, learner.getOrDefault("maxBins")
-                )
-                imodels, directions = fit_tree_forest(
-                    learner, f_edges, f_bins, res_label, res_weight, comm
-                )
+                f_edges, f_bins = binned.get(
+                    int(learner.getOrDefault("maxBins")))
+                bag_w = w
+                imodels = [fit_gbm_round_tree(
+                    learner, f_edges, f_bins, ylab, predictions, w, loss,
+                    wstats, comm,
+                )]
             else:
-                from ..parallel.streams import parallel_fits
-
-                def class_task(j):
-                    def task():
-                        fr = binned.fit_frame(
-                            learner, res_label[:, j].contiguous(),
-                            res_weight[:, j].contiguous(), idx, xs,
-                        )
-                        return self.fit_base_learner(
-                            learner, fr, weight_col="weight"
-                        )
-                    return task
-
-                imodels = parallel_fits(
-                    [class_task(j) for j in range(dim)],
-                    self.getOrDefault("parallelism"), warm_first=True,
+                bag_m = self.sample_weights(
+                    self.getReplacement(),
+                    self.getSubsampleRatio(),
+                    n,
+                    seed + i,
+                    device,
+                    None,
+                    comm.rank,
                 )
+                bag_w = bag_m * w
+
+                newton = use_newton and loss.has_hessian
+                g, h = loss.grad_hess_fused(ylab, predictions, want_hess=newton)
+                if newton:
+                    h = h.clamp_min(1e-2)  # [N, dim]
+                    sum_h = (h * bag_m.unsqueeze(1)).sum(dim=0)
+                    comm.all_reduce_(sum_h)
+                    res_label = -g / h  # [N, dim]
+                    res_weight = 0.5 * h / sum_h.unsqueeze(0) * bag_w.unsqueeze(1)
+                else:
+                    res_label = -g
+                    res_weight = bag_w.unsqueeze(1).expand(-1, dim)
+
+                # K per-class base-regressor fits.  The reference runs these
+                # as driver-side parallel futures (:377-411); here, when the
+                # base learner is the built-in histogram tree, ALL K trees
+                # grow level-synchronously in fused kernel launches (ONE
+                # histogram build + ONE all-reduce per level for the whole
+                # round — tree_grower.grow_forest).  Generic base learners
+                # keep the sequential per-class path.
+                if dim > 1 and self._can_fuse_round(learner, res_weight,
+                                                    fuse_state):
+                    from ..models.tree import fit_tree_forest
+
+                    f_edges, f_bins = binned.sliced_binned(
+                        idx, learner.getOrDefault("maxBins")
+                    )
+                    imodels, directions = fit_tree_forest(
+                        learner, f_edges, f_bins, res_label, res_weight, comm
+                    )
+                else:
+                    from ..parallel.streams import parallel_fits
+
+                    def class_task(j):
+                        def task():
+                            fr = binned.fit_frame(
+                                learner, res_label[:, j].contiguous(),
+                                res_weight[:, j].contiguous(), idx, xs,
+                            )
+                            return self.fit_base_learner(
+                                learner, fr, weight_col="weight"
+                            )
+                        return task
+
+                    imodels = parallel_fits(
+                        [class_task(j) for j in range(dim)],
+                        self.getOrDefault("parallelism"), warm_first=True,
+                    )
 
             if directions is None:
                 def _dir(m):

@@ -200,31 +200,101 @@ def _fused_fit_stats(grad, w, comm):
     d = grad.shape[1]
     n = grad.shape[0]
     dev = grad.device
-    sums = torch.cat([
-        w.sum().reshape(1),
-        (w == 0).sum().reshape(1).to(torch.float32),
-        (w != 1).sum().reshape(1).to(torch.float32),
-        torch.tensor([float(n)], device=dev),
-        grad.sum(dim=0).reshape(-1),
-    ])
+    w_sums, w_max = _weight_stat_parts(w)
+    sums = torch.cat([w_sums, grad.sum(dim=0).reshape(-1)])
     maxs = torch.cat([
         grad.abs().amax(dim=0).reshape(-1) if n else torch.zeros(d, device=dev),
-        w.abs().amax().reshape(1) if n else torch.zeros(1, device=dev),
+        w_max,
     ])
     if comm.is_distributed:
         comm.all_reduce_(sums)
         comm.all_reduce_(maxs, "max")
     sums_c = sums.cpu()
     maxs_c = maxs.cpu()
+    st = _weight_stats_dict(sums_c[:4], maxs_c[d:])
+    st["gsum"] = sums_c[4:]
+    st["gmax"] = maxs_c[:d]
+    return st
+
+
+def _weight_stat_parts(w):
+    """Device halves of the weight statistics: the sums (total weight, zero
+    count, non-unit count, local row count) and the ``|w|`` maximum."""
+    n = w.shape[0]
+    dev = w.device
+    sums = torch.cat([
+        w.sum().reshape(1),
+        (w == 0).sum().reshape(1).to(torch.float32),
+        (w != 1).sum().reshape(1).to(torch.float32),
+        torch.tensor([float(n)], device=dev),
+    ])
+    w_max = w.abs().amax().reshape(1) if n else torch.zeros(1, device=dev)
+    return sums, w_max
+
+
+def _weight_stats_dict(sums_c, max_c):
     return {
         "total_w": float(sums_c[0]),
         "has_zero": float(sums_c[1]) > 0,
         "all_one": float(sums_c[2]) == 0,
         "n_global": float(sums_c[3]),
-        "gsum": sums_c[4:],
-        "gmax": maxs_c[:d],
-        "hmax": float(maxs_c[d]),
+        "hmax": float(max_c[0]),
     }
+
+
+def fit_weight_stats(w, comm):
+    """The weight half of ``_fused_fit_stats`` on its own: what a tree fit
+    needs to know about the row weights (global total, any zero, all one,
+    ``|w|`` maximum, global row count).  A GBM fit on full bags takes it once,
+    before its rounds: the weights do not change between them."""
+    sums, w_max = _weight_stat_parts(w)
+    if comm.is_distributed:
+        comm.all_reduce_(sums)
+        comm.all_reduce_(w_max, "max")
+    return _weight_stats_dict(sums.cpu(), w_max.cpu())
+
+
+def fit_gbm_round_tree(learner, edges, bins, label, pred, weight, loss,
+                       wstats, comm):
+    """The base-learner fit of one dim-1 gradient GBM round on full bags,
+    from the margins: ``ops.gbm_round_prologue`` writes the weighted negative
+    gradient, the grower's gradient matrix and ``max |grad|`` in one pass, so
+    the round skips the bag weights, ``-g``, the fit frame, ``w * y``, the
+    weight statistics (``wstats`` from ``fit_weight_stats``, taken once per
+    fit) and the grower's ``cat``.  The gradient total stays ``grad.sum``:
+    its summation order reaches every leaf value through the root totals.
+    Same tree, bit for bit, as ``DecisionTreeRegressor`` fitted on (``-g``,
+    ``weight``); ``_train_pred`` is set on the returned model.
+
+    Caller contract: a plain ``DecisionTreeRegressor`` with
+    ``minWeightFractionPerNode == 0``, GPU tensors, no zero weight."""
+    from .tree_grower import grow_forest
+
+    assert not wstats["has_zero"], "fit_gbm_round_tree: zero weights"
+    gh, grad, gmax = ops.gbm_round_prologue(
+        label, pred, weight, loss, wstats["all_one"])
+    # the [N, 1] reduction DecisionTreeRegressor._fit runs, over the same values
+    gsum = grad.unsqueeze(1).sum(dim=0).reshape(-1)
+    if comm.is_distributed:
+        comm.all_reduce_(gsum)
+        comm.all_reduce_(gmax, "max")
+    stats_c = torch.cat([gsum, gmax]).cpu()  # the round's one host sync
+    st = dict(wstats, gsum=stats_c[:1], gmax=stats_c[1:])
+    gp = learner._grow_params(st["total_w"])
+    hic, gh_max, root_tot = _grow_args(st)
+    tp_out: list = []
+    tree = grow_forest(
+        bins, edges, grad.unsqueeze(1), weight, gp, comm, hic, tp_out, gh_max,
+        root_tot_in=root_tot.reshape(1, -1), gh_in=gh,
+    )[0]
+    model = DecisionTreeRegressionModel()
+    model._set_tree(tree, bins.shape[1])
+    model._train_pred = tp_out[0].squeeze(1)
+    # the column names fit_base_learner gives the learner's copy
+    model.set("featuresCol", "features")
+    model.set("labelCol", "label")
+    model.set("predictionCol", "prediction")
+    return model
 
 
 def _grow_args(st):

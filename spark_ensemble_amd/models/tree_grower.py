@@ -578,6 +578,7 @@ def grow_forest(
     root_tot_in: Optional[torch.Tensor] = None,  # [T, C] GLOBAL cpu totals
     class_labels: Optional[torch.Tensor] = None,  # [N] class ids (class mode)
     num_classes: int = 0,
+    gh_in: Optional[torch.Tensor] = None,  # [N, T * C] finished gh matrix
 ) -> List[Dict[str, torch.Tensor]]:
     """Grow T single-output trees LEVEL-SYNCHRONOUSLY in fused launches.
 
@@ -605,6 +606,11 @@ def grow_forest(
     layout, so split search, sibling subtraction, partition and leaf
     finalisation are the shared code below.  ``gh_max_in``, when given,
     only supplies the weight maximum (its largest entry).
+
+    ``gh_in``: the interleaved [N, T * C] gradient matrix, already built by
+    the caller from these ``grads`` and ``hess`` (the GBM round prologue
+    writes it in the pass that computes the gradients); it is used as it is
+    instead of being assembled here.
     """
     device = bins.device
     N, F = bins.shape
@@ -625,6 +631,7 @@ def grow_forest(
     # [n_active, F, B, C] level histogram) stays modest
     batch_cap = MAX_FUSED_TREES if D == 1 else max(2, (MAX_FUSED_TREES * 3) // (D + 2))
     if T > batch_cap:
+        assert gh_in is None, "gh_in covers one fused batch"
         out: List[Dict[str, torch.Tensor]] = []
         preds = [] if train_pred_out is not None else None
         for s in range(0, T, batch_cap):
@@ -671,12 +678,17 @@ def grow_forest(
     else:
         assert C <= 8, f"fused forest: D + hess/count channels = {C} > 8"
         g3 = grads if grads.dim() == 3 else grads.unsqueeze(2)
-        parts = [g3, (hess.unsqueeze(1).expand(N, T) if h_shared else hess)
-                 .unsqueeze(2)]
-        if NN == 2:
-            parts.append(
-                torch.ones(N, T, 1, dtype=torch.float32, device=device))
-        gh = torch.cat(parts, dim=2).reshape(N, T * C).contiguous()
+        if gh_in is not None:
+            assert gh_in.shape == (N, T * C) and gh_in.is_contiguous()
+            gh = gh_in
+        else:
+            parts = [g3,
+                     (hess.unsqueeze(1).expand(N, T) if h_shared else hess)
+                     .unsqueeze(2)]
+            if NN == 2:
+                parts.append(
+                    torch.ones(N, T, 1, dtype=torch.float32, device=device))
+            gh = torch.cat(parts, dim=2).reshape(N, T * C).contiguous()
 
         if gh_max_in is not None:
             gh_max = gh_max_in  # slot-wise [C] host tensor

@@ -283,6 +283,52 @@ def split_search(hist, lam=1e-6, min_child_weight=0.0, min_instances=1.0, min_in
     return reference.split_search(hist, lam, min_child_weight, min_instances, min_info_gain, d_dims)
 
 
+def round_fused_enabled() -> bool:
+    """``SEA_ROUND_FUSED=0`` keeps the dim-1 GBM round on its composed
+    prologue (sample_weights, grad_hess, neg, mul, the base learner's fit
+    statistics and the grower's cat); read at every call."""
+    return os.environ.get("SEA_ROUND_FUSED", "1") != "0"
+
+
+def gbm_round_prologue_geometry(n):
+    """(threads per block, blocks) of the native gbm_round_prologue at ``n``
+    rows; one trip of its grid-stride loop covers threads * blocks rows."""
+    m = _require_hip("gbm_round_prologue_geometry")
+    if m is None:
+        raise RuntimeError("gbm_round_prologue_geometry needs the HIP "
+                           "extension")
+    threads, blocks = m.gbm_round_prologue_geometry(int(n))
+    return int(threads), int(blocks)
+
+
+def gbm_round_prologue(label, pred, weight, loss, unit_weight):
+    """What a dim-1 gradient-boosting round needs from its rows before the
+    tree grows, in one pass: ``(gh, grad, gmax)`` with ``grad = weight *
+    (-g)`` [N] for the gradient ``g`` of the scalar ``loss`` at (``label``,
+    ``pred``) [N, 1], ``gh`` the grower's [N, C] matrix (``(grad, weight)``
+    when ``unit_weight``, a fact about ``weight`` the caller vouches for,
+    else ``(grad, weight, 1)``) and ``gmax`` the one-element ``max |grad|``,
+    NaN when a gradient is NaN.  The gradient sum is left to the caller
+    (``grad.sum``): its order is part of the fitted model."""
+    if pred.is_cuda:
+        m = _require_hip("gbm_round_prologue")
+        if m is not None:
+            n = pred.shape[0]
+            c = 2 if unit_weight else 3
+            gh = torch.empty(n, c, dtype=torch.float32, device=pred.device)
+            grad = torch.empty(n, dtype=torch.float32, device=pred.device)
+            if n == 0:  # a 0-block grid is not a valid launch
+                return gh, grad, grad.new_zeros(1)
+            gmax = torch.empty(1, dtype=torch.float32, device=pred.device)
+            m.gbm_round_prologue(
+                gh, grad, gmax, label.contiguous(), pred.contiguous(),
+                weight.contiguous(), loss.loss_id, float(loss.param),
+                bool(unit_weight),
+            )
+            return gh, grad, gmax
+    return reference.gbm_round_prologue(label, pred, weight, loss, unit_weight)
+
+
 def level_fused_enabled() -> bool:
     """``SEA_LEVEL_FUSED=0`` keeps the tree level loop on the composed ops
     (assemble + split_search + pack, device-side left counts); read at every

@@ -584,6 +584,22 @@ def logreg_loss_grad(x, y_int, w, wmat, has_bias):
     return torch.cat([nll.reshape(1), gw.reshape(-1), gb.reshape(-1)])
 
 
+def gbm_round_prologue(label, pred, weight, loss, unit_weight):
+    """The composed form of one dim-1 GBM round's prologue
+    (dispatch.gbm_round_prologue contract): ``grad = weight * (-g)`` [N] for
+    the loss gradient ``g``, the grower's ``gh`` matrix ``(grad, weight)``
+    [N, 2] under unit weights or ``(grad, weight, 1)`` [N, 3], and
+    ``max |grad|`` as a one-element tensor (NaN when a gradient is NaN)."""
+    g = loss.grad_hess_fused(label, pred, want_hess=False)[0]
+    grad = weight * (-g).squeeze(1)
+    parts = [grad.unsqueeze(1), weight.unsqueeze(1)]
+    if not unit_weight:
+        parts.append(torch.ones_like(parts[0]))
+    gh = torch.cat(parts, dim=1).contiguous()
+    gmax = grad.abs().amax().reshape(1) if grad.numel() else grad.new_zeros(1)
+    return gh, grad, gmax
+
+
 # ---------------------------------------------------------------------------
 # Per-row feature contributions (path-dependent TreeSHAP; semantics in
 # docs/contributions.md)

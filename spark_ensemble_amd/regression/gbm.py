@@ -202,6 +202,8 @@ class GBMRegressor(Regressor, _GBMRegressorParams):
             i = r0
             instr.log_named_value("resumed_from_round", r0)
 
+        fuse_state: dict = {}  # fit-local, see _fused_round_wstats
+
         while i < k_stages and v < self.getOrDefault("numRounds"):
             if loss_name == "huber":
                 delta = dist_quantile((y - predictions).abs(), alpha, None, comm)
@@ -210,33 +212,50 @@ class GBMRegressor(Regressor, _GBMRegressorParams):
             idx = subspaces[i]
             xs = binned.sliced_features(idx)
 
-            # bag multiplicities (sampling only) and full weights
-            bag_m = self.sample_weights(
-                self.getReplacement(),
-                self.getSubsampleRatio(),
-                n,
-                seed + i,
-                device,
-                None,
-                comm.rank,
-            )
-            bag_w = bag_m * w
-
             ylab = y.unsqueeze(1)
             pred2 = predictions.unsqueeze(1)
-            newton = use_newton and loss.has_hessian
-            g, h = loss.grad_hess_fused(ylab, pred2, want_hess=newton)
-            if newton:
-                h = h.squeeze(1).clamp_min(1e-2)
-                sum_h = comm.all_reduce_scalar(float((h * bag_m).sum()))
-                res_label = -g.squeeze(1) / h
-                res_weight = 0.5 * h / sum_h * bag_w
-            else:
-                res_label = -g.squeeze(1)
-                res_weight = bag_w
 
-            fr = binned.fit_frame(learner, res_label, res_weight, idx, xs)
-            model = self.fit_base_learner(learner, fr, weight_col="weight")
+            # full bags: the round's base fit runs from the margins in one
+            # native pass (fit_gbm_round_tree); the bag multiplicities are
+            # exactly 1, so the bag weights are ``w``
+            wstats = self._fused_round_wstats(
+                learner, 1, idx, x, w, comm, fuse_state)
+            if wstats is not None:
+                from ..models.tree import fit_gbm_round_tree
+
+                f_edges, f_bins = binned.get(
+                    int(learner.getOrDefault("maxBins")))
+                bag_w = w
+                model = fit_gbm_round_tree(
+                    learner, f_edges, f_bins, ylab, pred2, w, loss, wstats,
+                    comm,
+                )
+            else:
+                # bag multiplicities (sampling only) and full weights
+                bag_m = self.sample_weights(
+                    self.getReplacement(),
+                    self.getSubsampleRatio(),
+                    n,
+                    seed + i,
+                    device,
+                    None,
+                    comm.rank,
+                )
+                bag_w = bag_m * w
+
+                newton = use_newton and loss.has_hessian
+                g, h = loss.grad_hess_fused(ylab, pred2, want_hess=newton)
+                if newton:
+                    h = h.squeeze(1).clamp_min(1e-2)
+                    sum_h = comm.all_reduce_scalar(float((h * bag_m).sum()))
+                    res_label = -g.squeeze(1) / h
+                    res_weight = 0.5 * h / sum_h * bag_w
+                else:
+                    res_label = -g.squeeze(1)
+                    res_weight = bag_w
+
+                fr = binned.fit_frame(learner, res_label, res_weight, idx, xs)
+                model = self.fit_base_learner(learner, fr, weight_col="weight")
 
             # tree base learners capture train-row predictions during
             # growth (leaf scatter) — avoids a full tree walk per round
