@@ -127,8 +127,8 @@ void logreg_loss_grad_wide(torch::Tensor payload, torch::Tensor x,
                            torch::Tensor y, torch::Tensor w,
                            torch::Tensor wmat, bool has_bias);
 bool logreg_wide_supported(int64_t F, int64_t K);
-std::tuple<int64_t, int64_t, int64_t, int64_t> logreg_wide_geometry(
-    int64_t F, int64_t K);
+std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>
+logreg_wide_geometry(int64_t F, int64_t K);
 
 // csrc/linear_gram.hip
 void linear_gram(torch::Tensor G, torch::Tensor x, torch::Tensor y,

@@ -420,12 +420,12 @@ __global__ __launch_bounds__(256) void logreg_wide_reduce_kernel(
 
 bool logreg_wide_supported(int64_t F, int64_t K) { return lw_plan(F, K).ok; }
 
-// (KP, S, rows per block tile, LDS bytes); all 0 where unsupported
-std::tuple<int64_t, int64_t, int64_t, int64_t> logreg_wide_geometry(
-    int64_t F, int64_t K) {
+// (KP, S, rows per block tile, LDS bytes, NT, db); all 0 where unsupported
+std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>
+logreg_wide_geometry(int64_t F, int64_t K) {
   const LwPlan p = lw_plan(F, K);
-  if (!p.ok) return {0, 0, 0, 0};
-  return {p.KP, p.S, (kLwWaves / p.S) * 16, (int64_t)p.lds};
+  if (!p.ok) return {0, 0, 0, 0, 0, 0};
+  return {p.KP, p.S, (kLwWaves / p.S) * 16, (int64_t)p.lds, p.NT, p.db};
 }
 
 void logreg_loss_grad_wide(torch::Tensor payload, torch::Tensor x,

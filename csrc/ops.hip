@@ -2192,7 +2192,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused logistic loss+gradient on f32 MFMA tiles, K <= 32, F <= 1024");
   m.def("logreg_wide_supported", &logreg_wide_supported);
   m.def("logreg_wide_geometry", &logreg_wide_geometry,
-        "(padded classes, feature slices, rows per block tile, LDS bytes) of "
+        "(padded classes, feature slices, rows per block tile, LDS bytes, "
+        "register tiles per wave, 1 if two X tiles fit in LDS) of "
         "logreg_loss_grad_wide");
   m.def("linear_gram", &linear_gram,
         "weighted Gram matrix of [x, 1, y] in f64 on f32 MFMA tiles, "

@@ -1621,6 +1621,9 @@ def forest_wquantile(x, trees, weights, probs, cache=None,
     return reference.forest_wquantile(x, trees, w32, probs)
 
 
+last_logreg_info: dict = {}
+
+
 def logreg_loss_grad(x, y_int, w, wmat, has_bias, native_only=False):
     """Single-pass fused logistic loss+gradient.
 
@@ -1634,10 +1637,15 @@ def logreg_loss_grad(x, y_int, w, wmat, has_bias, native_only=False):
     faster than the narrow one for K = 2..5 (profiles/logreg_wide.md) and it
     is bitwise reproducible, which the narrow kernel's f32 atomics are not.
 
+    Every call records what ran in ``last_logreg_info``: ``path`` is
+    "narrow", "wide" or "reference", and the six values of
+    ``logreg_wide_geometry`` follow (all 0 unless the path is "wide").
+
     ``native_only``: return None where the torch fallback would run.
     """
     f = x.shape[1]
     k = wmat.shape[1]
+    geometry = (0, 0, 0, 0, 0, 0)
     if x.is_cuda:
         m = _require_hip("logreg_loss_grad")
         if m is not None:
@@ -1646,13 +1654,14 @@ def logreg_loss_grad(x, y_int, w, wmat, has_bias, native_only=False):
                 payload = torch.zeros(
                     1 + (f + 1) * k, dtype=torch.float32, device=x.device
                 )
-                kernel = m.logreg_loss_grad
+                kernel, path = m.logreg_loss_grad, "narrow"
             elif wide:
                 # every entry is written by the slot reduction
                 payload = torch.empty(
                     1 + (f + 1) * k, dtype=torch.float32, device=x.device
                 )
-                kernel = m.logreg_loss_grad_wide
+                kernel, path = m.logreg_loss_grad_wide, "wide"
+                geometry = m.logreg_wide_geometry(f, k)
             else:
                 kernel = None
             if kernel is not None:
@@ -1660,10 +1669,19 @@ def logreg_loss_grad(x, y_int, w, wmat, has_bias, native_only=False):
                     payload, x.contiguous(), y_int.contiguous(),
                     w.contiguous(), wmat.contiguous(), bool(has_bias),
                 )
+                _set_logreg_info(path, geometry)
                 return payload
+    _set_logreg_info("reference", geometry)
     if native_only:
         return None
     return reference.logreg_loss_grad(x, y_int, w, wmat, has_bias)
+
+
+def _set_logreg_info(path, geometry):
+    kp, s, rows, lds, nt, db = geometry
+    last_logreg_info.update(
+        path=path, kp=kp, slices=s, rows_per_tile=rows, lds_bytes=lds,
+        nt=nt, db=db)
 
 
 last_weighted_gram_info: dict = {}
