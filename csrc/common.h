@@ -24,6 +24,18 @@ __device__ inline float sortable_f32(unsigned s) {
   return __uint_as_float(u);
 }
 
+// counter-based RNG of sample_weights (ops.hip) and goss_weights (goss.hip)
+__device__ inline uint64_t splitmix64(uint64_t z) {
+  z += 0x9e3779b97f4a7c15ull;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+
+__device__ inline float u01(uint64_t z) {
+  return ((z >> 40) + 1) * (1.0f / 16777216.0f);  // upper 24 bits -> (0, 1]
+}
+
 // Pinned ping-pong staging slots of h2d_async, one name per call site.
 // gather_ranges and leaf_scatter share a slot; every other site owns its.
 enum UploadSlot : int {
@@ -116,6 +128,14 @@ void gbm_round_prologue(torch::Tensor gh, torch::Tensor grad,
                         torch::Tensor pred, torch::Tensor weight,
                         int64_t loss_id, double param, bool unit_weight);
 std::tuple<int64_t, int64_t> gbm_round_prologue_geometry(int64_t n);
+
+// csrc/goss.hip
+void goss_weights(torch::Tensor bag, torch::Tensor g, torch::Tensor w,
+                  int64_t k, double p_other, double amp, int64_t seed,
+                  int64_t rank);
+std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+           int64_t>
+goss_geometry(int64_t n);
 
 // csrc/linear.hip
 void logreg_loss_grad(torch::Tensor payload, torch::Tensor x, torch::Tensor y,

@@ -76,19 +76,9 @@ torch::Tensor h2d_async(const void* src, size_t bytes, UploadSlot slot,
 }
 
 // ---------------------------------------------------------------------------
-// sample_weights: counter-based RNG (splitmix64), one state per row
+// sample_weights: counter-based RNG (splitmix64 / u01 of common.h), one state
+// per row
 // ---------------------------------------------------------------------------
-
-__device__ inline uint64_t splitmix64(uint64_t z) {
-  z += 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-
-__device__ inline float u01(uint64_t z) {
-  return ((z >> 40) + 1) * (1.0f / 16777216.0f);  // upper 24 bits -> (0, 1]
-}
 
 __global__ void sample_weights_kernel(float* __restrict__ out, int64_t n,
                                       int replacement, float ratio,
@@ -2253,6 +2243,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dim-1 GBM round: weighted negative gradient, gh matrix, max |grad|");
   m.def("gbm_round_prologue_geometry", &gbm_round_prologue_geometry,
         "(threads per block, blocks) of gbm_round_prologue at n rows");
+  m.def("goss_weights", &goss_weights,
+        "GOSS row multiplicities: exact top-k by radix select, Bernoulli rest");
+  m.def("goss_geometry", &goss_geometry,
+        "(rows per tile, tiles, blocks, digit bits x 3, slot bytes, block "
+        "cap) of goss_weights at n rows");
   m.def("line_search_eval", &line_search_eval, "fused loss+grad line-search payload");
   m.def("newton_chain_1d", &newton_chain_1d,
         "device-chained safeguarded-Newton stage-weight search");

@@ -17,6 +17,7 @@ from ..ensemble.params import (
 from ..params import Params, ParamValidators
 
 SUPPORTED_UPDATES = ["newton", "gradient"]
+SUPPORTED_SAMPLING = ["uniform", "goss"]
 
 
 class GBMParams(
@@ -61,6 +62,23 @@ class GBMParams(
             lower=False,
         )
         self.seed = self._int_param("seed", "random seed")
+        self.sampling = self._str_param(
+            "sampling",
+            "row sampling per round: uniform (subsampleRatio / replacement) "
+            "or goss (gradient-based one-side sampling)",
+            ParamValidators.inArray(SUPPORTED_SAMPLING),
+        )
+        self.topRate = self._float_param(
+            "topRate",
+            "goss: fraction of rows kept for their gradient magnitude",
+            ParamValidators.inRange(0.0, 1.0, False, False),
+        )
+        self.otherRate = self._float_param(
+            "otherRate",
+            "goss: fraction of rows drawn from the rest",
+            ParamValidators.inRange(0.0, 1.0, False, False),
+        )
+        self._setDefault(sampling="uniform", topRate=0.2, otherRate=0.1)
         self._setDefault(
             optimizedWeights=True,
             updates="gradient",
@@ -98,6 +116,7 @@ class GBMParams(
         if not (
             dim == 1
             and state["static_ok"]
+            and self.getOrDefault("sampling") == "uniform"
             and self.getOrDefault("updates") == "gradient"
             and self.getSubsampleRatio() >= 1.0
             and not self.getReplacement()
@@ -110,6 +129,47 @@ class GBMParams(
         if state.get("wstats") is None:
             state["wstats"] = fit_weight_stats(w, comm)
         return None if state["wstats"]["has_zero"] else state["wstats"]
+
+    def _check_sampling(self):
+        """What ``fit`` refuses under ``sampling="goss"``."""
+        if self.getOrDefault("sampling") != "goss":
+            return
+        top, other = self.getOrDefault("topRate"), self.getOrDefault("otherRate")
+        if top + other > 1.0:
+            raise ValueError(
+                f"goss: topRate + otherRate = {top + other} exceeds 1")
+        if self.getSubsampleRatio() != 1.0:
+            raise ValueError("goss: subsampleRatio must be 1, the rates of "
+                             "goss replace it")
+        if self.getReplacement():
+            raise ValueError("goss samples without replacement")
+
+    def _round_bag(self, g, w, seed, comm, instr):
+        """The bag multiplicities [N] of one round: Bernoulli / Poisson draws
+        under ``sampling="uniform"``, else GOSS on the round's gradients
+        ``g`` [N, dim] and the row weights ``w``, over this rank's rows."""
+        if self.getOrDefault("sampling") != "goss":
+            return self.sample_weights(
+                self.getReplacement(), self.getSubsampleRatio(), g.shape[0],
+                seed, g.device, None, comm.rank,
+            )
+        from ..ops import dispatch as ops
+
+        bag_m = ops.goss_weights(
+            g, w, self.getOrDefault("topRate"), self.getOrDefault("otherRate"),
+            seed, comm.rank,
+        )
+        instr.log_named_value("goss_kept_rows", int((bag_m > 0).sum()))
+        return bag_m
+
+    def setSampling(self, v):
+        return self.set("sampling", v)
+
+    def setTopRate(self, v):
+        return self.set("topRate", v)
+
+    def setOtherRate(self, v):
+        return self.set("otherRate", v)
 
     def setOptimizedWeights(self, v):
         return self.set("optimizedWeights", v)

@@ -98,6 +98,7 @@ class GBMClassifier(ProbabilisticClassifier, _GBMClassifierParams):
         instr = Instrumentation(self, dataset)
         instr.log_params(self, "loss", "numBaseLearners", "updates",
                          "learningRate", "optimizedWeights")
+        self._check_sampling()
         comm = get_comm()
         learner = self.getOrNone("baseLearner") or self._default_base_learner()
         seed = self.getOrDefault("seed")
@@ -229,19 +230,10 @@ class GBMClassifier(ProbabilisticClassifier, _GBMClassifierParams):
                     wstats, comm,
                 )]
             else:
-                bag_m = self.sample_weights(
-                    self.getReplacement(),
-                    self.getSubsampleRatio(),
-                    n,
-                    seed + i,
-                    device,
-                    None,
-                    comm.rank,
-                )
-                bag_w = bag_m * w
-
                 newton = use_newton and loss.has_hessian
                 g, h = loss.grad_hess_fused(ylab, predictions, want_hess=newton)
+                bag_m = self._round_bag(g, w, seed + i, comm, instr)
+                bag_w = bag_m * w
                 if newton:
                     h = h.clamp_min(1e-2)  # [N, dim]
                     sum_h = (h * bag_m.unsqueeze(1)).sum(dim=0)
@@ -379,6 +371,7 @@ class GBMClassifier(ProbabilisticClassifier, _GBMClassifierParams):
         learner = self.getOrNone("baseLearner") or self._default_base_learner()
         return (
             self.getOrDefault("updates") == "gradient"
+            and self.getOrDefault("sampling") == "uniform"
             and self.getSubspaceRatio() >= 1.0
             and self.getSubsampleRatio() >= 1.0
             and not self.getReplacement()

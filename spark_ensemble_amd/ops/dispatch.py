@@ -68,6 +68,41 @@ def sample_weights(replacement, ratio, n, seed, device=None, base_weight=None, r
     return reference.sample_weights(replacement, ratio, n, seed, device, base_weight, rank)
 
 
+def goss_geometry(n):
+    """How the native goss_weights cuts ``n`` rows: ``tile_rows`` consecutive
+    rows per tile, ``tiles``, ``blocks`` (block b takes tiles b, b + blocks,
+    ..., so one grid round covers ``blocks * tile_rows`` rows), the
+    ``digit_bits`` of the three radix passes, the ``slot_bytes`` of the
+    per-block histogram slots and ``max_blocks``, the grid cap."""
+    m = _require_hip("goss_geometry")
+    if m is None:
+        raise RuntimeError("goss_geometry needs the HIP extension")
+    tile, tiles, blocks, b0, b1, b2, slot_bytes, cap = m.goss_geometry(int(n))
+    return {"tile_rows": int(tile), "tiles": int(tiles),
+            "blocks": int(blocks), "digit_bits": (int(b0), int(b1), int(b2)),
+            "slot_bytes": int(slot_bytes), "max_blocks": int(cap)}
+
+
+def goss_weights(g, w, top_rate, other_rate, seed, rank=0):
+    """GOSS row multiplicities ``[N]`` f32 from the gradient matrix ``g``
+    [N, D] and the row weights ``w`` [N]; semantics in
+    ``reference.goss_weights`` and docs/gbm.md.  On the GPU the selection is
+    the radix select of csrc/goss.hip: no sort, no host sync."""
+    if g.is_cuda:
+        m = _require_hip("goss_weights")
+        if m is not None:
+            n = g.shape[0]
+            g2 = g.to(torch.float32).reshape(n, -1).contiguous()
+            k, p_other, amp = reference.goss_params(top_rate, other_rate, n)
+            out = torch.empty(n, dtype=torch.float32, device=g.device)
+            if n == 0:  # a 0-block grid is not a valid launch
+                return out
+            m.goss_weights(out, g2, w.to(torch.float32).contiguous(), k,
+                           p_other, amp, int(seed), int(rank))
+            return out
+    return reference.goss_weights(g, w, top_rate, other_rate, seed, rank)
+
+
 def quantile_bins(x, max_bins=256, sample_rows=262_144, seed=17):
     # sort-based; torch sort is fine on both devices (one-time cost per fit)
     return reference.quantile_bins(x, max_bins, sample_rows, seed)

@@ -11,8 +11,10 @@ maps ops -> reference call sites).
 
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Tuple
 
+import numpy as np
 import torch
 
 
@@ -51,6 +53,60 @@ def sample_weights(
     if base_weight is not None:
         w = w * base_weight
     return w
+
+
+def goss_params(top_rate: float, other_rate: float, n: int):
+    """(k, p_other, amp) of GOSS at ``n`` rows: the top-row count and, as the
+    f32 values both devices use, the draw probability of the other rows and
+    their amplification.  float64 arithmetic on the host."""
+    k = min(max(int(math.ceil(float(top_rate) * n)), 1), n)
+    p_other = np.float32(float(other_rate) / (1.0 - float(top_rate)))
+    amp = np.float32((1.0 - float(top_rate)) / float(other_rate))
+    return k, float(p_other), float(amp)
+
+
+def goss_keys(g: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """The int32 selection key of every row: the bits of ``(|g[:, 0]| +
+    |g[:, 1]| + ...) * w`` in f32, columns added left to right, sign bit
+    cleared; unsigned order of the bits is numeric order of non-negative
+    floats and NaN sorts above +inf.  Every NaN gets the one key 0x7fc00000."""
+    s = g[:, 0].abs()
+    for c in range(1, g.shape[1]):
+        s = s + g[:, c].abs()
+    v = (s * w).contiguous()
+    key = v.view(torch.int32) & 0x7FFFFFFF
+    return key.masked_fill_(v.isnan(), 0x7FC00000)
+
+
+def goss_weights(g, w, top_rate, other_rate, seed, rank=0) -> torch.Tensor:
+    """Gradient-based one-side sampling as a multiplicity vector ``[N]`` f32
+    (docs/gbm.md): 1 for the ``k = ceil(top_rate * N)`` rows of largest key
+    (``goss_keys``), ties at the k-th key going to the lower row index; each
+    other row ``amp = (1 - top_rate) / other_rate`` with probability
+    ``other_rate / (1 - top_rate)``, else 0.  The draw is the counter-based
+    splitmix64 stream of the native ``sample_weights``, mirrored in uint64,
+    so csrc/goss.hip returns the same vector bit for bit."""
+    dev = g.device
+    g = g.detach().to("cpu", torch.float32).reshape(g.shape[0], -1)
+    w = w.detach().to("cpu", torch.float32)
+    n = g.shape[0]
+    k, p_other, amp = goss_params(top_rate, other_rate, n)
+    order = torch.sort(goss_keys(g, w), descending=True, stable=True)[1]
+    m64 = (1 << 64) - 1
+    with np.errstate(over="ignore"):
+        i1 = np.arange(1, n + 1, dtype=np.uint64)
+        s = np.uint64((seed * 0x100000001B3 + rank * 0x9E3779B9) & m64)
+        z = (s ^ (np.uint64(0x9E3779B97F4A7C15) * i1)) \
+            + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    u = ((z >> np.uint64(40)) + np.uint64(1)).astype(np.float32) \
+        * np.float32(1.0 / 16777216.0)
+    out = torch.from_numpy(
+        np.where(u <= np.float32(p_other), np.float32(amp), np.float32(0.0)))
+    out[order[:k]] = 1.0
+    return out.to(dev)
 
 
 # ---------------------------------------------------------------------------

@@ -107,6 +107,7 @@ class GBMRegressor(Regressor, _GBMRegressorParams):
         instr = Instrumentation(self, dataset)
         instr.log_params(self, "loss", "numBaseLearners", "updates",
                          "learningRate", "optimizedWeights")
+        self._check_sampling()
         comm = get_comm()
         learner = (
             self.getOrNone("baseLearner") or self._default_base_learner()
@@ -231,20 +232,11 @@ class GBMRegressor(Regressor, _GBMRegressorParams):
                     comm,
                 )
             else:
-                # bag multiplicities (sampling only) and full weights
-                bag_m = self.sample_weights(
-                    self.getReplacement(),
-                    self.getSubsampleRatio(),
-                    n,
-                    seed + i,
-                    device,
-                    None,
-                    comm.rank,
-                )
-                bag_w = bag_m * w
-
                 newton = use_newton and loss.has_hessian
                 g, h = loss.grad_hess_fused(ylab, pred2, want_hess=newton)
+                # bag multiplicities (sampling only) and full weights
+                bag_m = self._round_bag(g, w, seed + i, comm, instr)
+                bag_w = bag_m * w
                 if newton:
                     h = h.squeeze(1).clamp_min(1e-2)
                     sum_h = comm.all_reduce_scalar(float((h * bag_m).sum()))
@@ -339,6 +331,7 @@ class GBMRegressor(Regressor, _GBMRegressorParams):
             self.getLoss() == "squared"
             and self.getOrDefault("initStrategy") == "constant"
             and self.getOrDefault("updates") == "gradient"
+            and self.getOrDefault("sampling") == "uniform"
             and self.getSubspaceRatio() >= 1.0
             and self.getSubsampleRatio() >= 1.0
             and not self.getReplacement()

@@ -30,6 +30,7 @@ SRC = [
     os.path.join(REPO, "csrc", "forest_permute.hip"),
     os.path.join(REPO, "csrc", "forest_wquantile.hip"),
     os.path.join(REPO, "csrc", "gbm_round.hip"),
+    os.path.join(REPO, "csrc", "goss.hip"),
 ]
 # Sources compiled on their own, with flags the rest is not built with.
 # forest_wquantile.hip: packed f32 instructions (v_pk_add/mul/fma_f32) off.
@@ -48,12 +49,15 @@ SRC = [
 # gbm_round.hip: the same guard; one scalar multiply per row next to the loss
 # gradient of csrc/gbm_loss.h, whose bits tests/test_round_prologue_gpu.py
 # compares with the grad_hess kernel of ops.hip.
+# goss.hip: the same guard; its f32 arithmetic is the |g| sum and one multiply
+# by the row weight, whose bits the host mirror in ops/reference.py repeats.
 _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SRC_FLAGS = {
     "forest_wquantile.hip": _NO_PACKED_F32,
     "linear_wide.hip": _NO_PACKED_F32,
     "linear_gram.hip": _NO_PACKED_F32,
     "gbm_round.hip": _NO_PACKED_F32,
+    "goss.hip": _NO_PACKED_F32,
 }
 OUT = os.path.join(REPO, "spark_ensemble_amd", "_hip_ops.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
