@@ -40,7 +40,7 @@ __device__ inline float u01(uint64_t z) {
 // gather_ranges and leaf_scatter share a slot; every other site owns its.
 enum UploadSlot : int {
   kSlotHistChunks = 0,      // hist_build: scales + chunk table
-  kSlotHistNodes = 1,       // hist_build: staging slot -> node
+  kSlotLevelPlan = 1,       // level_plan: per-child table
   kSlotPartCursors = 2,     // partition_rows: per-node cursors
   kSlotPartChunks = 3,      // partition_rows: chunk table
   kSlotPartSegStart = 4,    // partition_rows: segment starts
@@ -60,7 +60,8 @@ torch::Tensor h2d_async(const void* src, size_t bytes, UploadSlot slot,
 
 // csrc/ops.hip: decode the i64 staging sums of multi-chunk nodes into f32,
 // out[nodes[slot]] = stage[slot] / scales[channel]; nodes and scales are
-// device pointers
+// device pointers.  nodes == nullptr: scales heads hist_build's table, whose
+// slot records name the nodes and whose header bounds the live slots
 void launch_hist_decode(float* out, const long long* stage, const int* nodes,
                         const float* scales, int n_multi, int64_t FBC, int C,
                         hipStream_t stream);

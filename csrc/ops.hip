@@ -235,8 +235,10 @@ void bin_features(torch::Tensor out, torch::Tensor x, torch::Tensor edges) {
 //   impossible since low fields are non-negative and bounded).
 //
 //   chunks: int32 [n_chunks, 5] = (node, start, len, stage_slot, col0)
-//   as planned by csrc/hist_plan.h; quantization scales ride in the same
-//   upload (one H2D per launch).  ``col0`` is the node's base column in a gh matrix of row
+//   as planned by csrc/hist_plan.h, on the host or by level_plan_kernel; the
+//   table's 2 C header words in front of them hold the C quantization scales,
+//   the record count and the slot count (one H2D per host-planned launch).
+//   ``col0`` is the node's base column in a gh matrix of row
 //   stride CH — 0/CH==C for single-tree builds; a FOREST build (K trees
 //   or K classes grown level-synchronously, reference
 //   GBMClassifier.scala:377-411 parallel futures) interleaves per-tree
@@ -297,6 +299,11 @@ __global__ void hist_build_kernel(
   constexpr int CELLS = DC > NC ? DC : NC;
   extern __shared__ unsigned long long lds64[];  // FG * B * CELLS
   const float* scales = reinterpret_cast<const float*>(chunks);
+  // header: scales [0, C), record count, slot count.  A grid sized by the
+  // planner's bound (device-planned levels) has surplus blocks: they leave
+  // before touching LDS
+  const int n_chunks = chunks[C];
+  if ((int)blockIdx.x >= n_chunks) return;
   const int* chk = chunks + 2 * C + blockIdx.x * 5;
   const int fg = blockIdx.y;
   const int f0 = fg * FG;
@@ -417,7 +424,7 @@ __global__ void hist_build_kernel(
         // multi-chunk node: the LDS image goes as it stands, 16 B per lane,
         // into this block's slab; hist_reduce_kernel sums the node's slabs.
         // slot record = (node, first record, record count, first slab)
-        const int* srec = chunks + 2 * C + (int)gridDim.x * 5 + slot * 4;
+        const int* srec = chunks + 2 * C + n_chunks * 5 + slot * 4;
         const int64_t slab =
             (int64_t)(srec[3] + (int)blockIdx.x - srec[1]) * gridDim.y + fg;
         uint4* dst = reinterpret_cast<uint4*>(partial + slab * lds_cells);
@@ -486,13 +493,24 @@ __global__ void hist_build_kernel(
   }
 }
 
-// decode the i64 staging sums of multi-chunk nodes into f32 out
+// decode the i64 staging sums of multi-chunk nodes into f32 out.  ``nodes``
+// is the node of each slot, or null: then ``scales`` is the head of
+// hist_build's table, the nodes are read from its slot records, and grid y is
+// only a bound on the slot count of its header.
 __global__ void hist_decode_kernel(float* __restrict__ out,
                                    const long long* __restrict__ stage,
-                                   const int* __restrict__ nodes,  // [n_multi] node of each slot
+                                   const int* __restrict__ nodes,
                                    const float* __restrict__ scales,  // [C]
                                    int64_t FBC, int C) {
-  const int64_t obase = (int64_t)nodes[blockIdx.y] * FBC;
+  int node;
+  if (nodes) {
+    node = nodes[blockIdx.y];
+  } else {
+    const int* chunks = reinterpret_cast<const int*>(scales);
+    if ((int)blockIdx.y >= chunks[C + 1]) return;
+    node = chunks[2 * C + chunks[C] * 5 + blockIdx.y * 4];
+  }
+  const int64_t obase = (int64_t)node * FBC;
   const int64_t sbase = (int64_t)blockIdx.y * FBC;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < FBC;
        i += gridDim.x * (int64_t)blockDim.x) {
@@ -509,6 +527,18 @@ void launch_hist_decode(float* out, const long long* stage, const int* nodes,
                      stream, out, stage, nodes, scales, FBC, C);
 }
 
+// zero the staging of the live slots of a device-planned level (the slot
+// count is in the table header; grid y is its bound)
+__global__ void hist_stage_clear_kernel(long long* __restrict__ stage,
+                                        const int* __restrict__ n_live,
+                                        int64_t FBC) {
+  if ((int)blockIdx.y >= *n_live) return;
+  long long* s = stage + (int64_t)blockIdx.y * FBC;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < FBC;
+       i += gridDim.x * (int64_t)blockDim.x)
+    s[i] = 0;
+}
+
 // Sum the LDS-image slabs of each multi-chunk node of the bin-major path and
 // convert: out[node, f, b, :] = (float)(int64 sum over the node's records of
 // the fields of partial[slab, group of f][cell][b][f % FG]) / scale.  The
@@ -518,12 +548,16 @@ void launch_hist_decode(float* out, const long long* stage, const int* nodes,
 __global__ void hist_reduce_kernel(
     float* __restrict__ out,                         // [n_nodes, F, B, C]
     const unsigned long long* __restrict__ partial,  // slabs
-    const int* __restrict__ slots,   // [n_multi, 4] node, first, count, slab
-    const float* __restrict__ scales,  // [C]
+    const int* __restrict__ chunks,  // hist_build's table: header, records,
+                                     // then [n_multi, 4] node, first, count,
+                                     // slab
     int F, int B, int FG, int DC, int NC) {
-  const int* srec = slots + blockIdx.y * 4;
-  const int node = srec[0], count = srec[2];
   const int C = DC + NC, CELLS = DC > NC ? DC : NC;
+  // grid y is a bound on the slot count of the header
+  if ((int)blockIdx.y >= chunks[C + 1]) return;
+  const float* scales = reinterpret_cast<const float*>(chunks);
+  const int* srec = chunks + 2 * C + chunks[C] * 5 + blockIdx.y * 4;
+  const int node = srec[0], count = srec[2];
   const int n_groups = F / FG;
   const int nbt = (B + 7) >> 3;
   const int group_tiles = (FG >> 3) * nbt;
@@ -559,6 +593,132 @@ __global__ void hist_reduce_kernel(
 // wide rows can outgrow that.  Above this bound the launch falls back to the
 // staged atomics.
 constexpr int64_t kHistPartialMaxBytes = (int64_t)1 << 30;
+
+// Launch geometry of hist_build_kernel for F features, B bins and D + NN
+// channels; a function of the shapes alone, so a host-planned and a
+// device-planned level of one fit agree on it.
+struct HistGeom {
+  int FG, threads, n_groups, CELLS;
+  size_t lds_bytes;
+  bool bin_major;   // the vectorised kernel
+  bool slab_flush;  // multi-chunk nodes may flush as slabs
+};
+
+static HistGeom hist_geometry(int F, int B, int D, int NN) {
+  const int CELLS = std::max(D, NN);
+  // feature-group size by CELLS, probe-measured
+  // (profiles/r01_hist_probe3): CELLS==1 -> FG=64 / 1024 threads / 128 KiB
+  // LDS (1 block/CU; 64-B row slices quarter the random-row fetch
+  // amplification); CELLS==2 -> FG=32 / 1024; CELLS>=3 (multiclass) ->
+  // FG=16 / 512 in ~99 KiB, which keeps the vectorized uint4 row loads.
+  // SEA_HIST_FG caps FG, SEA_HIST_LDS the LDS budget.
+  static const int fg_env = []() {
+    const char* e = getenv("SEA_HIST_FG");
+    return e ? atoi(e) : 0;
+  }();
+  static const int lds_budget = []() {
+    const char* e = getenv("SEA_HIST_LDS");
+    return e ? atoi(e) : 163840;  // up to the full 160 KiB LDS per CU
+  }();
+  int FG = std::max<int>(1, std::min<int>(F, lds_budget / (B * CELLS * 8)));
+  if (CELLS == 1 && FG >= 64 && (F % 64) == 0) FG = 64;
+  else if (CELLS <= 2 && FG >= 32 && (F % 32) == 0) FG = 32;
+  else if (FG >= 16) FG = 16;
+  else if (FG >= 8) FG = 8;
+  else if (FG >= 4) FG = 4;
+  if (fg_env == 16 || fg_env == 32 || fg_env == 64)
+    FG = std::min(FG, fg_env);
+  HistGeom g;
+  g.FG = FG;
+  g.CELLS = CELLS;
+  g.threads = (FG >= 64 || (CELLS == 2 && FG >= 32)) ? 1024
+              : ((FG >= 32 || (CELLS >= 3 && FG >= 16)) ? 512 : 256);
+  g.n_groups = (int)ceil_div(F, FG);
+  g.lds_bytes = (size_t)FG * B * CELLS * 8;
+  // full 16-aligned groups take the vectorised bin-major kernel (FG <= 64 /
+  // 32 / 16 for CELLS 1 / 2 / >= 3 by the choice above, as it assumes)
+  g.bin_major = (FG == 16 || FG == 32 || FG == 64) && (F % FG) == 0;
+  TORCH_CHECK(!g.bin_major ||
+                  FG <= (CELLS == 1 ? 64 : (CELLS == 2 ? 32 : 16)),
+              "hist_build: FG ", FG, " too wide for CELLS ", CELLS);
+  g.slab_flush = g.bin_major && CELLS == 1;  // kHistSlabFlush
+  return g;
+}
+
+// hist_build_kernel over grid_x chunk blocks of the table ``chunks``, then
+// the pass that finishes its multi-chunk nodes: hist_reduce_kernel over the
+// slabs of ``partial`` when that is defined, else hist_decode_kernel over
+// ``stage`` when that is.  grid_x and n_slots may exceed the record and slot
+// counts of the table's header; the kernels read those.
+static void hist_launch(const HistGeom& g, int D, int NN, int grid_x,
+                        int n_slots, torch::Tensor out, torch::Tensor stage,
+                        torch::Tensor partial, torch::Tensor bins,
+                        torch::Tensor gh, torch::Tensor row_idx,
+                        torch::Tensor chunks, int B, bool identity_rows,
+                        bool gh_by_position) {
+  const int F = (int)bins.size(1), CH = (int)gh.size(1), C = D + NN;
+  const int FG = g.FG, threads = g.threads, n_groups = g.n_groups;
+  const size_t lds_bytes = g.lds_bytes;
+  const bool bin_major = g.bin_major;
+  long long* stage_ptr =
+      stage.defined() ? reinterpret_cast<long long*>(stage.data_ptr<int64_t>())
+                      : nullptr;
+  unsigned long long* partial_ptr =
+      partial.defined() ? reinterpret_cast<unsigned long long*>(
+                              partial.data_ptr<int64_t>())
+                        : nullptr;
+  auto stream = at::hip::getCurrentHIPStream();
+#define HB_LAUNCH_L(DD, NNN, BM)                                             \
+  do {                                                                       \
+    if (lds_bytes > 65536)                                                   \
+      (void)hipFuncSetAttribute(                                             \
+          reinterpret_cast<const void*>(&hist_build_kernel<DD, NNN, BM>),    \
+          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);       \
+    hipLaunchKernelGGL((hist_build_kernel<DD, NNN, BM>),                     \
+                       dim3(grid_x, n_groups), dim3(threads),                \
+                       lds_bytes, stream, out.data_ptr<float>(), stage_ptr,  \
+                       partial_ptr, bins.data_ptr<uint8_t>(),                \
+                       gh.data_ptr<float>(), row_idx.data_ptr<int>(),        \
+                       chunks.data_ptr<int>(), F, B, FG, CH,                 \
+                       identity_rows ? 1 : 0, gh_by_position ? 1 : 0);       \
+  } while (0)
+#define HB_LAUNCH(DD, NNN)                                                   \
+  do {                                                                       \
+    if (bin_major) HB_LAUNCH_L(DD, NNN, true);                               \
+    else HB_LAUNCH_L(DD, NNN, false);                                        \
+  } while (0)
+  const int key = D * 10 + NN;
+  switch (key) {
+    case 11: HB_LAUNCH(1, 1); break;
+    case 12: HB_LAUNCH(1, 2); break;
+    case 21: HB_LAUNCH(2, 1); break;
+    case 22: HB_LAUNCH(2, 2); break;
+    case 31: HB_LAUNCH(3, 1); break;
+    case 32: HB_LAUNCH(3, 2); break;
+    case 41: HB_LAUNCH(4, 1); break;
+    case 42: HB_LAUNCH(4, 2); break;
+    case 51: HB_LAUNCH(5, 1); break;
+    case 52: HB_LAUNCH(5, 2); break;
+    case 61: HB_LAUNCH(6, 1); break;
+    case 62: HB_LAUNCH(6, 2); break;
+    case 71: HB_LAUNCH(7, 1); break;
+    default: TORCH_CHECK(false, "hist_build: unsupported D/NN ", D, "/", NN);
+  }
+#undef HB_LAUNCH
+#undef HB_LAUNCH_L
+  if (n_slots == 0) return;
+  if (partial_ptr) {
+    const int64_t lanes = (int64_t)n_groups * (FG >> 3) * ((B + 7) >> 3) * 64;
+    hipLaunchKernelGGL(hist_reduce_kernel,
+                       dim3((unsigned)ceil_div(lanes, 256), n_slots),
+                       dim3(256), 0, stream, out.data_ptr<float>(),
+                       partial_ptr, chunks.data_ptr<int>(), F, B, FG, D, NN);
+  } else if (stage_ptr) {
+    launch_hist_decode(out.data_ptr<float>(), stage_ptr, nullptr,
+                       reinterpret_cast<const float*>(chunks.data_ptr<int>()),
+                       n_slots, (int64_t)F * B * C, C, stream);
+  }
+}
 
 // Returns the number of multi-chunk nodes.  ``gh_by_position``: gh is the
 // compact [row_idx.numel(), CH] matrix of gather_ranges_gh, read by position.
@@ -596,35 +756,9 @@ int64_t hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
                   (!identity_rows && gh.size(0) == row_idx.numel()),
               "gh_by_position: gh must have one row per row_idx entry");
   if (n_nodes == 0 || F == 0) return 0;
-  const int CELLS = std::max(D, NN);
-
-  // feature-group size by CELLS, probe-measured
-  // (profiles/r01_hist_probe3): CELLS==1 -> FG=64 / 1024 threads / 128 KiB
-  // LDS (1 block/CU; 64-B row slices quarter the random-row fetch
-  // amplification); CELLS==2 -> FG=32 / 1024; CELLS>=3 (multiclass) ->
-  // FG=16 / 512 in ~99 KiB, which keeps the vectorized uint4 row loads.
-  // SEA_HIST_FG caps FG, SEA_HIST_LDS the LDS budget.
-  static const int fg_env = []() {
-    const char* e = getenv("SEA_HIST_FG");
-    return e ? atoi(e) : 0;
-  }();
-  static const int lds_budget = []() {
-    const char* e = getenv("SEA_HIST_LDS");
-    return e ? atoi(e) : 163840;  // up to the full 160 KiB LDS per CU
-  }();
-  int FG = std::max<int>(1, std::min<int>(F, lds_budget / (B * CELLS * 8)));
-  if (CELLS == 1 && FG >= 64 && (F % 64) == 0) FG = 64;
-  else if (CELLS <= 2 && FG >= 32 && (F % 32) == 0) FG = 32;
-  else if (FG >= 16) FG = 16;
-  else if (FG >= 8) FG = 8;
-  else if (FG >= 4) FG = 4;
-  if (fg_env == 16 || fg_env == 32 || fg_env == 64)
-    FG = std::min(FG, fg_env);
-  const int threads =
-      (FG >= 64 || (CELLS == 2 && FG >= 32)) ? 1024
-      : ((FG >= 32 || (CELLS >= 3 && FG >= 16)) ? 512 : 256);
-  const int n_groups = (int)ceil_div(F, FG);
-  const size_t lds_bytes = (size_t)FG * B * CELLS * 8;
+  const HistGeom g = hist_geometry(F, B, D, NN);
+  const int n_groups = g.n_groups;
+  const size_t lds_bytes = g.lds_bytes;
 
   HistPlan plan = plan_hist_chunks(
       node_offsets.data_ptr<int64_t>(), n_nodes,
@@ -632,34 +766,24 @@ int64_t hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
       identity_rows ? bins.size(0) : row_idx.numel(), CH - C + 1, lds_bytes,
       n_groups, 2 * C);
 
-  // full 16-aligned groups take the vectorised bin-major kernel (FG <= 64 /
-  // 32 / 16 for CELLS 1 / 2 / >= 3 by the choice above, as it assumes)
-  const bool bin_major =
-      (FG == 16 || FG == 32 || FG == 64) && (F % FG) == 0;
-  TORCH_CHECK(!bin_major || FG <= (CELLS == 1 ? 64 : (CELLS == 2 ? 32 : 16)),
-              "hist_build: FG ", FG, " too wide for CELLS ", CELLS);
-
   // staging slot records after the chunk records: (node, first record,
   // record count, first slab); a node's slabs follow its records' order
   const int n_multi = (int)plan.multi_nodes.size();
-  const size_t slots_at = plan.table.size();
   int64_t n_slabs = 0;
-  for (int s = 0; s < n_multi; ++s) {
-    const int rec[4] = {plan.multi_nodes[s], plan.slot_first[s],
-                        plan.slot_count[s], (int)n_slabs};
-    plan.table.insert(plan.table.end(), rec, rec + 4);
-    n_slabs += plan.slot_count[s];
-  }
+  for (int c : plan.slot_count) n_slabs += c;
+  plan.table.insert(plan.table.end(), plan.slots.begin(), plan.slots.end());
   const int64_t partial_bytes = n_slabs * n_groups * (int64_t)lds_bytes;
-  const bool use_partial = bin_major && CELLS == 1 /* kHistSlabFlush */ &&
-                           n_multi && partial_bytes <= kHistPartialMaxBytes;
+  const bool use_partial = g.slab_flush && n_multi &&
+                           partial_bytes <= kHistPartialMaxBytes;
 
-  // header: per-channel quantization scales
+  // header: per-channel quantization scales, record count, slot count
   auto max_abs_f = max_abs.to(torch::kFloat32).contiguous();
   auto ma = max_abs_f.accessor<float, 1>();
   float* scales_f = reinterpret_cast<float*>(plan.table.data());
   for (int c = 0; c < C; ++c)
     scales_f[c] = (float)hist_fixed_scale(plan.chunk_rows, ma[c]);
+  plan.table[C] = plan.n_chunks;
+  plan.table[C + 1] = n_multi;
   auto chunks = h2d_async(plan.table.data(), plan.table.size() * 4,
                           kSlotHistChunks, bins.device())
                     .view(torch::kInt32);
@@ -669,74 +793,14 @@ int64_t hist_build(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
   // atomics add into.  Integer sums either way, so histograms are bitwise
   // deterministic.
   torch::Tensor stage, partial;
-  long long* stage_ptr = nullptr;
-  unsigned long long* partial_ptr = nullptr;
-  if (use_partial) {
+  if (use_partial)
     partial = torch::empty({partial_bytes / 8},
                            out.options().dtype(torch::kInt64));
-    partial_ptr =
-        reinterpret_cast<unsigned long long*>(partial.data_ptr<int64_t>());
-  } else if (n_multi) {
+  else if (n_multi)
     stage = torch::zeros({(int64_t)n_multi, (int64_t)F, (int64_t)B, (int64_t)C},
                          out.options().dtype(torch::kInt64));
-    stage_ptr = reinterpret_cast<long long*>(stage.data_ptr<int64_t>());
-  }
-
-  auto stream = at::hip::getCurrentHIPStream();
-#define HB_LAUNCH_L(DD, NNN, BM)                                             \
-  do {                                                                       \
-    if (lds_bytes > 65536)                                                   \
-      (void)hipFuncSetAttribute(                                             \
-          reinterpret_cast<const void*>(&hist_build_kernel<DD, NNN, BM>),    \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);       \
-    hipLaunchKernelGGL((hist_build_kernel<DD, NNN, BM>),                     \
-                       dim3(plan.n_chunks, n_groups), dim3(threads),         \
-                       lds_bytes, stream, out.data_ptr<float>(), stage_ptr,  \
-                       partial_ptr, bins.data_ptr<uint8_t>(),                \
-                       gh.data_ptr<float>(), row_idx.data_ptr<int>(),        \
-                       chunks.data_ptr<int>(), F, B, FG, CH,                 \
-                       identity_rows ? 1 : 0, gh_by_position ? 1 : 0);       \
-  } while (0)
-#define HB_LAUNCH(DD, NNN)                                                   \
-  do {                                                                       \
-    if (bin_major) HB_LAUNCH_L(DD, NNN, true);                               \
-    else HB_LAUNCH_L(DD, NNN, false);                                        \
-  } while (0)
-  const int key = D * 10 + NN;
-  switch (key) {
-    case 11: HB_LAUNCH(1, 1); break;
-    case 12: HB_LAUNCH(1, 2); break;
-    case 21: HB_LAUNCH(2, 1); break;
-    case 22: HB_LAUNCH(2, 2); break;
-    case 31: HB_LAUNCH(3, 1); break;
-    case 32: HB_LAUNCH(3, 2); break;
-    case 41: HB_LAUNCH(4, 1); break;
-    case 42: HB_LAUNCH(4, 2); break;
-    case 51: HB_LAUNCH(5, 1); break;
-    case 52: HB_LAUNCH(5, 2); break;
-    case 61: HB_LAUNCH(6, 1); break;
-    case 62: HB_LAUNCH(6, 2); break;
-    case 71: HB_LAUNCH(7, 1); break;
-    default: TORCH_CHECK(false, "hist_build: unsupported D/NN ", D, "/", NN);
-  }
-#undef HB_LAUNCH
-#undef HB_LAUNCH_L
-  if (use_partial) {
-    const int64_t lanes = (int64_t)n_groups * (FG >> 3) * ((B + 7) >> 3) * 64;
-    hipLaunchKernelGGL(hist_reduce_kernel,
-                       dim3((unsigned)ceil_div(lanes, 256), n_multi),
-                       dim3(256), 0, stream, out.data_ptr<float>(),
-                       partial_ptr, chunks.data_ptr<int>() + slots_at,
-                       reinterpret_cast<const float*>(chunks.data_ptr<int>()),
-                       F, B, FG, D, NN);
-  } else if (n_multi) {
-    auto nodes = h2d_async(plan.multi_nodes.data(), (size_t)n_multi * 4,
-                           kSlotHistNodes, bins.device());
-    launch_hist_decode(out.data_ptr<float>(), stage_ptr,
-                       (const int*)nodes.data_ptr(),
-                       reinterpret_cast<const float*>(chunks.data_ptr<int>()),
-                       n_multi, (int64_t)F * B * C, C, stream);
-  }
+  hist_launch(g, D, NN, plan.n_chunks, n_multi, out, stage, partial, bins, gh,
+              row_idx, chunks, B, identity_rows, gh_by_position);
   return n_multi;
 }
 
@@ -1198,6 +1262,9 @@ __global__ void gather_ranges_gh_kernel(
   const long long* cum = seg;
   const long long* starts = seg + n_segs + 1;
   const long long* col0 = starts + n_segs;
+  // total < 0: the ranges were planned on the device (level_plan_kernel),
+  // out is sized by a bound and the grid with it
+  if (total < 0) total = cum[n_segs];
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
        p < total; p += stride) {
@@ -1332,6 +1399,278 @@ void leaf_scatter(torch::Tensor tp, torch::Tensor row_idx,
                      (const long long*)seg_b.data_ptr(),
                      (const int*)tree_b.data_ptr(),
                      (const float*)val_b.data_ptr(), T, n_segs, total);
+}
+
+// ---------------------------------------------------------------------------
+// level_plan: the next level's ranges and histogram table, planned on the
+// device right behind partition_kernel.  Which child of each split pair is
+// built, the shapes and the launch geometry follow from the split results the
+// host already has; only the children's row counts come from the partition,
+// and waiting for them on the host left the GPU idle between levels
+// (profiles/level_chain.md).  One block: thread i owns built child i, block
+// scans give its compact offset, first record, slot and first slab, and the
+// records are written by the functions of csrc/hist_plan.h the host planner
+// uses.
+//   child: int32 [n, 5] = (pair, 1 if right child, gh col0, parent start,
+//          parent end); the pair's left cursor of ``cursors`` [n_pairs, 2] is
+//          where its left rows end in the partitioned arena
+//   seg:   int64 [3n + 1] = compact offsets b_off [n + 1], source starts
+//          [n], gh col0 [n] -- what gather_ranges_gh_kernel reads
+//   table: hist_build_kernel's table over the compact rows (col0 0)
+// ---------------------------------------------------------------------------
+
+struct GhMax8 { float v[8]; };
+
+constexpr int kPlanThreads = 256;
+
+// exclusive prefix of v over the block, the block's sum in *total
+__device__ inline long long plan_scan(long long v, long long* sh,
+                                      long long* total) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int d = 1; d < kPlanThreads; d <<= 1) {
+    const long long a = t >= d ? sh[t - d] : 0;
+    __syncthreads();
+    sh[t] += a;
+    __syncthreads();
+  }
+  const long long incl = sh[t];
+  *total = sh[kPlanThreads - 1];
+  __syncthreads();
+  return incl - v;
+}
+
+__global__ void level_plan_kernel(int* __restrict__ table,
+                                  long long* __restrict__ seg,
+                                  const int* __restrict__ cursors,
+                                  const int* __restrict__ child, int n,
+                                  long long target_chunks, int max_chunks,
+                                  int C, GhMax8 gh_max) {
+  __shared__ long long sh[kPlanThreads];
+  // rows [s, s + len) of child i in the partitioned arena; the cursor is
+  // clamped into its parent's range, so the lens sum to at most the parents'
+  // rows whatever the cursor table holds
+  auto range = [&](int i, long long& s, long long& len) {
+    const int* ch = child + 5 * i;
+    const int ps = ch[3], pe = ch[4];
+    const int le = min(max(cursors[2 * ch[0]], ps), pe);
+    s = ch[1] ? le : ps;
+    len = ch[1] ? pe - le : le - ps;
+  };
+  long long total = 0;
+  for (int base = 0; base < n; base += kPlanThreads) {
+    const int i = base + threadIdx.x;
+    long long s = 0, len = 0, tile;
+    if (i < n) range(i, s, len);
+    const long long ex = plan_scan(len, sh, &tile);
+    if (i < n) {
+      seg[i] = total + ex;
+      seg[n + 1 + i] = s;
+      seg[2 * n + 1 + i] = child[5 * i + 2];
+    }
+    total += tile;
+  }
+  if (threadIdx.x == 0) seg[n] = total;
+  const long long chunk_rows = hist_chunk_rows(total, target_chunks);
+
+  // first walk: the record count, which places the slot records; second
+  // walk: emit
+  int n_chunks = 0, n_slots = 0;
+  for (int emit = 0; emit < 2; ++emit) {
+    int* slots = table + 2 * C + 5 * n_chunks;
+    long long rec0 = 0, slot0 = 0, slab0 = 0;
+    for (int base = 0; base < n; base += kPlanThreads) {
+      const int i = base + threadIdx.x;
+      long long s = 0, len = 0, t_rec, t_slot, t_slab;
+      if (i < n) range(i, s, len);
+      const bool multi = i < n && hist_node_is_multi(len, chunk_rows);
+      const int nrec = i < n ? hist_node_records(len, chunk_rows) : 0;
+      const long long rec = rec0 + plan_scan(nrec, sh, &t_rec);
+      const long long slot = slot0 + plan_scan(multi ? 1 : 0, sh, &t_slot);
+      const long long slab = slab0 + plan_scan(multi ? nrec : 0, sh, &t_slab);
+      if (emit && i < n)
+        hist_emit_node(table + 2 * C + 5 * rec, slots + 4 * slot, i, seg[i],
+                       len, 0, chunk_rows, (int)rec, multi ? (int)slot : -1,
+                       (int)slab);
+      rec0 += t_rec;
+      slot0 += t_slot;
+      slab0 += t_slab;
+    }
+    n_chunks = (int)rec0;
+    n_slots = (int)slot0;
+    // cannot happen (hist_chunk_bound); an empty plan rather than a write
+    // past the table if it does
+    if (n_chunks > max_chunks) { n_chunks = n_slots = 0; break; }
+  }
+  if (threadIdx.x == 0) {
+    float* scales = reinterpret_cast<float*>(table);
+    for (int c = 0; c < C; ++c)
+      scales[c] = (float)hist_fixed_scale(chunk_rows, (double)gh_max.v[c]);
+    table[C] = n_chunks;
+    table[C + 1] = n_slots;
+    for (int c = C + 2; c < 2 * C; ++c) table[c] = 0;
+  }
+}
+
+// Shapes of a device-planned level: what the host can say before the
+// partition has run.  R bounds the rows of the built children.
+struct LevelPlanShape {
+  HistGeom g;
+  int64_t target_chunks, max_chunks;
+};
+
+static LevelPlanShape level_plan_shape(int64_t n, int64_t R, int F, int B,
+                                       int D, int NN) {
+  LevelPlanShape s;
+  s.g = hist_geometry(F, B, D, NN);
+  s.target_chunks = hist_target_chunks(s.g.lds_bytes, s.g.n_groups);
+  s.max_chunks = hist_chunk_bound(R, s.target_chunks, n);
+  return s;
+}
+
+// Queues level_plan_kernel; returns (table, seg) on the device.  ``child`` is
+// the host table above, ``src_rows`` the size of the partitioned arena its
+// ranges lie in, ``gh_cols`` the width its col0 + C must fit.
+std::tuple<torch::Tensor, torch::Tensor> level_plan(
+    torch::Tensor cursors, torch::Tensor child, torch::Tensor max_abs,
+    int64_t R, int64_t src_rows, int64_t gh_cols, int64_t F, int64_t num_bins,
+    int64_t d_dims, int64_t c_per_node) {
+  CHECK_GPU(cursors); CHECK_CONTIG(cursors);
+  TORCH_CHECK(cursors.scalar_type() == torch::kInt32 && cursors.dim() == 2 &&
+                  cursors.size(1) == 2,
+              "level_plan: cursors is the int32 [n_pairs, 2] partition table");
+  TORCH_CHECK(!child.is_cuda() && child.scalar_type() == torch::kInt32 &&
+                  child.dim() == 2 && child.size(1) == 5 &&
+                  child.is_contiguous(),
+              "level_plan: child is a host int32 [n, 5] table");
+  TORCH_CHECK(!max_abs.is_cuda(), "max_abs stays on host");
+  const int C = (int)c_per_node, D = (int)d_dims, NN = C - D;
+  TORCH_CHECK(C <= 8 && D >= 1 && NN >= 1 && NN <= 2 &&
+                  max_abs.numel() == C,
+              "level_plan: channels must be D grads + 1-2 nonneg, C <= 8, "
+              "one max_abs each");
+  const int64_t n = child.size(0), n_pairs = cursors.size(0);
+  TORCH_CHECK(n >= 1 && R >= 0 && R < ((int64_t)1 << 31) &&
+                  src_rows < ((int64_t)1 << 31),
+              "level_plan: no child, or rows past int32");
+  auto ch = child.accessor<int, 2>();
+  int64_t parent_rows = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    TORCH_CHECK(ch[i][0] >= 0 && ch[i][0] < n_pairs &&
+                    (ch[i][1] == 0 || ch[i][1] == 1),
+                "level_plan: bad pair or side of child ", i);
+    TORCH_CHECK(ch[i][2] >= 0 && ch[i][2] + C <= gh_cols,
+                "level_plan: col0 of child ", i, " outside gh");
+    TORCH_CHECK(ch[i][3] >= 0 && ch[i][3] <= ch[i][4] && ch[i][4] <= src_rows,
+                "level_plan: parent range of child ", i, " outside the arena");
+    parent_rows += ch[i][4] - ch[i][3];
+  }
+  TORCH_CHECK(parent_rows <= R, "level_plan: parents hold more than R rows");
+  const LevelPlanShape s =
+      level_plan_shape(n, R, (int)F, (int)num_bins, D, NN);
+  TORCH_CHECK(s.max_chunks < ((int64_t)1 << 24), "level_plan: too many chunks");
+  auto child_d = h2d_async(child.data_ptr(), (size_t)n * 20, kSlotLevelPlan,
+                           cursors.device());
+  auto table = torch::empty({2 * C + 5 * s.max_chunks + 4 * n},
+                            cursors.options());
+  auto seg = torch::empty({3 * n + 1}, cursors.options().dtype(torch::kInt64));
+  GhMax8 gm = {};
+  auto max_abs_f = max_abs.to(torch::kFloat32).contiguous();
+  for (int c = 0; c < C; ++c) gm.v[c] = max_abs_f.data_ptr<float>()[c];
+  hipLaunchKernelGGL(level_plan_kernel, dim3(1), dim3(kPlanThreads), 0,
+                     at::hip::getCurrentHIPStream(), table.data_ptr<int>(),
+                     (long long*)seg.data_ptr<int64_t>(),
+                     cursors.data_ptr<int>(), (const int*)child_d.data_ptr(),
+                     (int)n, (long long)s.target_chunks, (int)s.max_chunks, C,
+                     gm);
+  return {table, seg};
+}
+
+// hist_build from a level_plan table: out [n, F, B, C] over the compact
+// rows ``row_idx`` / ``gh`` ([R] / [R, C], filled up to the planned total).
+// The grid is hist_chunk_bound; partial and the staging are sized by it.
+void hist_build_planned(torch::Tensor out, torch::Tensor bins,
+                        torch::Tensor gh, torch::Tensor row_idx,
+                        torch::Tensor table, int64_t num_bins,
+                        int64_t d_dims) {
+  CHECK_GPU(out); CHECK_GPU(bins); CHECK_GPU(gh); CHECK_GPU(row_idx);
+  CHECK_GPU(table);
+  CHECK_CONTIG(out); CHECK_CONTIG(bins); CHECK_CONTIG(gh); CHECK_CONTIG(row_idx);
+  CHECK_CONTIG(table);
+  TORCH_CHECK(out.dim() == 4 && gh.dim() == 2 && bins.dim() == 2,
+              "hist_build_planned: out [n, F, B, C], gh [R, C], bins [N, F]");
+  const int64_t n = out.size(0), R = row_idx.numel();
+  const int F = (int)bins.size(1), B = (int)num_bins, C = (int)gh.size(1);
+  const int D = (int)d_dims, NN = C - D;
+  TORCH_CHECK(C <= 8 && D >= 1 && NN >= 1 && NN <= 2,
+              "hist_build_planned: channels must be D grads + 1-2 nonneg");
+  TORCH_CHECK(out.size(1) == F && out.size(2) == B && out.size(3) == C &&
+                  gh.size(0) == R && n >= 1 && F >= 1,
+              "hist_build_planned: shapes disagree");
+  const LevelPlanShape s = level_plan_shape(n, R, F, B, D, NN);
+  TORCH_CHECK(table.scalar_type() == torch::kInt32 &&
+                  table.numel() == 2 * C + 5 * s.max_chunks + 4 * n,
+              "hist_build_planned: table is not level_plan's for these "
+              "shapes");
+  // a multi-chunk node has more than chunk_rows >= 4096 rows, and fewer of
+  // them exist than total / chunk_rows (hist_chunk_bound)
+  const int64_t max_slots =
+      std::min<int64_t>({n, R / 4096, s.max_chunks - n});
+  torch::Tensor stage, partial;
+  if (max_slots > 0) {
+    const int64_t partial_bytes =
+        s.max_chunks * s.g.n_groups * (int64_t)s.g.lds_bytes;
+    if (s.g.slab_flush && partial_bytes <= kHistPartialMaxBytes) {
+      partial = torch::empty({partial_bytes / 8},
+                             out.options().dtype(torch::kInt64));
+    } else {
+      const int64_t FBC = (int64_t)F * B * C;
+      stage = torch::empty({max_slots, FBC},
+                           out.options().dtype(torch::kInt64));
+      hipLaunchKernelGGL(
+          hist_stage_clear_kernel,
+          dim3((unsigned)std::min<int64_t>(ceil_div(FBC, 256), 1024),
+               (unsigned)max_slots),
+          dim3(256), 0, at::hip::getCurrentHIPStream(),
+          reinterpret_cast<long long*>(stage.data_ptr<int64_t>()),
+          table.data_ptr<int>() + C + 1, FBC);
+    }
+  }
+  hist_launch(s.g, D, NN, (int)s.max_chunks, (int)max_slots, out, stage,
+              partial, bins, gh, row_idx, table, B, false, true);
+}
+
+// One device-planned level: plan, gather the built children's rows and
+// gradients out of the partitioned arena, build their histograms.  Nothing
+// here waits for the partition that fills ``cursors`` and ``new_rows``.
+void level_chain_hist(torch::Tensor out, torch::Tensor bins, torch::Tensor gh,
+                      torch::Tensor new_rows, torch::Tensor cursors,
+                      torch::Tensor child, torch::Tensor max_abs, int64_t R,
+                      int64_t num_bins, int64_t d_dims) {
+  CHECK_GPU(out); CHECK_GPU(gh); CHECK_GPU(new_rows);
+  CHECK_CONTIG(gh); CHECK_CONTIG(new_rows);
+  TORCH_CHECK(out.dim() == 4 && gh.dim() == 2 &&
+                  new_rows.scalar_type() == torch::kInt32,
+              "level_chain_hist: out [n, F, B, C], gh [N, CH], int32 rows");
+  const int C = (int)out.size(3), n = (int)child.size(0);
+  TORCH_CHECK(out.size(0) == n, "level_chain_hist: one out row per child");
+  auto [table, seg] =
+      level_plan(cursors, child, max_abs, R, new_rows.numel(), gh.size(1),
+                 out.size(1), num_bins, d_dims, C);
+  auto rows = torch::empty({R}, new_rows.options());
+  auto gh_b = torch::empty({R, (int64_t)C}, gh.options());
+  if (R > 0) {
+    const int blocks =
+        (int)std::min<long long>(8192, ceil_div(R, (int64_t)1024));
+    hipLaunchKernelGGL(gather_ranges_gh_kernel, dim3(blocks), dim3(256), 0,
+                       at::hip::getCurrentHIPStream(), rows.data_ptr<int>(),
+                       gh_b.data_ptr<float>(), new_rows.data_ptr<int>(),
+                       gh.data_ptr<float>(),
+                       (const long long*)seg.data_ptr<int64_t>(), n,
+                       (long long)-1, C, (int)gh.size(1));
+  }
+  hist_build_planned(out, bins, gh_b, rows, table, num_bins, d_dims);
 }
 
 // ---------------------------------------------------------------------------
@@ -2168,9 +2507,47 @@ std::tuple<torch::Tensor, torch::Tensor> hist_plan_slots_debug(
           torch::tensor(plan.slot_count, i32)};
 }
 
+// the host's fixed-point scales for a chunk size, as hist_build uploads them
+torch::Tensor hist_scales_debug(int64_t chunk_rows, torch::Tensor max_abs) {
+  auto ma = max_abs.to(torch::kFloat32).contiguous();
+  auto out = torch::empty_like(ma);
+  for (int64_t c = 0; c < ma.numel(); ++c)
+    out.data_ptr<float>()[c] =
+        (float)hist_fixed_scale(chunk_rows, ma.data_ptr<float>()[c]);
+  return out;
+}
+
+// hist_chunk_bound and the target chunk count for a launch geometry
+std::tuple<int64_t, int64_t> hist_chunk_bound_debug(int64_t R, int64_t n_nodes,
+                                                    int64_t lds_bytes,
+                                                    int64_t n_groups) {
+  const int64_t target = hist_target_chunks((size_t)lds_bytes, (int)n_groups);
+  return {hist_chunk_bound(R, target, n_nodes), target};
+}
+
+// (FG, threads, feature groups, LDS bytes) of hist_build at these shapes
+std::tuple<int64_t, int64_t, int64_t, int64_t> hist_geometry_debug(
+    int64_t F, int64_t B, int64_t D, int64_t NN) {
+  const HistGeom g = hist_geometry((int)F, (int)B, (int)D, (int)NN);
+  return {g.FG, g.threads, g.n_groups, (int64_t)g.lds_bytes};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("_hist_plan", &hist_plan_debug,
         "host-side chunk plan of the histogram kernels (no device)");
+  m.def("_hist_scales", &hist_scales_debug,
+        "host-side fixed-point scales of a chunk size (no device)");
+  m.def("_hist_chunk_bound", &hist_chunk_bound_debug,
+        "(record bound, target chunks) of a level of at most R rows");
+  m.def("_hist_geometry", &hist_geometry_debug,
+        "(FG, threads, feature groups, LDS bytes) of hist_build");
+  m.def("level_plan", &level_plan,
+        "ranges and histogram table of the next level, planned on the "
+        "device from the partition's cursor table");
+  m.def("hist_build_planned", &hist_build_planned,
+        "hist_build from a level_plan table, bounded grid");
+  m.def("level_chain_hist", &level_chain_hist,
+        "level_plan + gather_ranges_gh + hist_build_planned in one call");
   m.def("_hist_plan_slots", &hist_plan_slots_debug,
         "first record and record count of each staging slot of _hist_plan");
   m.def("gather_ranges_gh", &gather_ranges_gh,

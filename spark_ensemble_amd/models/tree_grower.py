@@ -456,6 +456,10 @@ def _grow_tree_seq(
 
 MAX_FUSED_TREES = 32  # bounds the [T*N] row-index arena per fused batch
 
+# levels whose histogram build grow_forest queued from a device-side plan
+# (SEA_LEVEL_CHAIN); tests read it to tell which path a fit took
+level_chain_stats = {"levels": 0}
+
 
 def _finish_level_split(
     built: Optional[torch.Tensor],  # [n_built, F, B, C] LOCAL sums (or None)
@@ -812,6 +816,9 @@ def grow_forest(
         and ops.level_fused_enabled()
     )
     parent_row_t: Optional[torch.Tensor] = None  # cpu long: row in ``hists``
+    # device-planned levels: the generic histogram kernel on the fused path
+    chain = fused and not class_mode and ops.level_chain_enabled()
+    chain_bh: Optional[torch.Tensor] = None  # next level's built histograms
 
     def _finalize_and_capture(idx_t, offs, ridx):
         if idx_t.numel() == 0:
@@ -879,7 +886,10 @@ def grow_forest(
             built_cpu = built_mask_t.nonzero(as_tuple=True)[0]
             nb_cpu = (~built_mask_t).nonzero(as_tuple=True)[0]
             bh = None
-            if built_cpu.numel():
+            if chain_bh is not None:
+                # queued behind the previous level's partition
+                bh, chain_bh = chain_bh, None
+            elif built_cpu.numel():
                 starts = offsets[built_cpu]
                 lens = offsets[built_cpu + 1] - starts
                 b_off = torch.zeros(built_cpu.numel() + 1, dtype=torch.int64)
@@ -967,6 +977,30 @@ def grow_forest(
 
         s_idx = do_split.nonzero(as_tuple=True)[0]  # cpu long, sorted
         t_ids = node_tree[s_idx]
+        # the built child of each pair is the smaller by the count channel
+        l_st = left_stats[s_idx]                       # [n_split, C]
+        r_st = totals[s_idx] - l_st
+        right = l_st[:, idx_c] > r_st[:, idx_c]
+
+        # chained level (profiles/level_chain.md): every node split, so which
+        # child of each pair is built and where its parent's rows lie is
+        # known here; only the children's row counts are still in the
+        # partition's cursor table.  A device kernel plans the next level's
+        # histogram build from that table, so the build is queued now, ahead
+        # of the rest of the bookkeeping, and the cursor read below no longer
+        # leaves the GPU empty.
+        if (chain and pr_async is not None
+                and int(s_idx.numel()) == n_active
+                and depth + 1 < params.max_depth):
+            child = torch.stack([
+                torch.arange(n_active, dtype=torch.int64),
+                right.to(torch.int64), t_ids * C, offsets[:-1], offsets[1:],
+            ], dim=1).to(torch.int32)
+            chain_bh = ops.level_chain_hist(
+                bins, gh, pr_async[0], pr_async[1][2], child, gh_max,
+                int(offsets[-1]), B, D, C)
+            level_chain_stats["levels"] += 1
+
         nids = node_nid[s_idx]
         f_l = feat_cpu[s_idx].long()
         b_l = b_cpu[s_idx].long()
@@ -990,12 +1024,8 @@ def grow_forest(
         # everything that depends only on the SPLIT results happens here,
         # while the partition kernel is still running; only the offsets
         # math below needs its left counts
-        l_st = left_stats[s_idx]                       # [n_split, C]
-        r_st = totals[s_idx] - l_st
         totals = torch.stack([l_st, r_st], dim=1).reshape(-1, C)
-        l_cnt = l_st[:, idx_c]
-        r_cnt = r_st[:, idx_c]
-        built_mask_t = torch.stack([l_cnt <= r_cnt, l_cnt > r_cnt],
+        built_mask_t = torch.stack([l_st[:, idx_c] <= r_st[:, idx_c], right],
                                    dim=1).reshape(-1)
         parent_of_t = torch.arange(s_idx.numel(),
                                    dtype=torch.long).repeat_interleave(2)

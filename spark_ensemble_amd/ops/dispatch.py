@@ -371,6 +371,59 @@ def level_fused_enabled() -> bool:
     return os.environ.get("SEA_LEVEL_FUSED", "1") != "0"
 
 
+def level_chain_enabled() -> bool:
+    """``SEA_LEVEL_CHAIN=0`` keeps every tree level planned on the host, after
+    the partition's row counts have arrived; read at every call."""
+    return os.environ.get("SEA_LEVEL_CHAIN", "1") != "0"
+
+
+def level_plan(cursors, child, max_abs, rows_bound, src_rows, gh_cols,
+               num_features, num_bins, d_dims, c_per_node):
+    """Plan the next level's histogram build on the device.
+
+    ``cursors`` is the partition's device cursor table [n_pairs, 2] (it may
+    still be being written), ``child`` a host int32 [n, 5] table of (pair,
+    1 if right child, gh col0, parent start, parent end) per built child,
+    ``rows_bound`` at least the rows of those parents.  Returns the device
+    tables (table, seg): ``table`` is what ``hist_build_planned`` launches
+    from -- C scales, the record and slot counts, padding to 2 C words, the
+    chunk records, the slot records -- and ``seg`` the int64 [3 n + 1]
+    compact offsets, source starts and col0 of the ranges to gather."""
+    m = _require_hip("level_plan")
+    return m.level_plan(
+        cursors, child.to(torch.int32).cpu().contiguous(),
+        max_abs.to(torch.float32).cpu(), int(rows_bound), int(src_rows),
+        int(gh_cols), int(num_features), int(num_bins), int(d_dims),
+        int(c_per_node),
+    )
+
+
+def hist_build_planned(bins, gh, row_idx, table, n_nodes, num_bins, d_dims):
+    """``hist_build_forest(..., gh_by_position=True)`` from a ``level_plan``
+    table: gh [R, C] and row_idx [R] are filled up to the planned total, the
+    grid is sized by the planner's bound."""
+    m = _require_hip("hist_build_planned")
+    out = torch.empty(n_nodes, bins.shape[1], num_bins, gh.shape[1],
+                      dtype=torch.float32, device=bins.device)
+    m.hist_build_planned(out, bins, gh, row_idx, table, int(num_bins),
+                         int(d_dims))
+    return out
+
+
+def level_chain_hist(bins, gh, new_rows, cursors, child, max_abs, rows_bound,
+                     num_bins, d_dims, c_per_node):
+    """The built children's histograms [n, F, B, C] of the next level, queued
+    behind the partition that fills ``new_rows`` and ``cursors`` without
+    waiting for it: ``level_plan``, the gather of their rows and gradients,
+    ``hist_build_planned``.  ``child`` as in :func:`level_plan`."""
+    m = _require_hip("level_chain_hist")
+    out = torch.empty(child.shape[0], bins.shape[1], num_bins, c_per_node,
+                      dtype=torch.float32, device=bins.device)
+    m.level_chain_hist(out, bins, gh, new_rows, cursors, child, max_abs,
+                       int(rows_bound), int(num_bins), int(d_dims))
+    return out
+
+
 def _check_level_table(table, n_built, n_prev):
     """The checks of the native level_split, for the composed path."""
     tb = table.tolist()
@@ -533,7 +586,8 @@ def partition_rows_async(bins, row_idx, node_offsets, feat, thr):
         cur_h.copy_(cursors, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        return new_rows, (cur_h, ev), offs_cpu
+        # the device table rides along for level_chain_hist
+        return new_rows, (cur_h, ev, cursors), offs_cpu
     left_counts = torch.zeros(n, dtype=torch.int32, device=bins.device)
     if _prof:
         _t1 = _time.perf_counter()
@@ -635,7 +689,7 @@ def leaf_scatter(tp, row_idx, starts, lens, tree, val):
 def partition_rows_finish(new_rows, left_counts, offs_cpu):
     n = offs_cpu.numel() - 1
     if isinstance(left_counts, tuple):
-        lc_h, ev = left_counts
+        lc_h, ev = left_counts[:2]
         ev.synchronize()
         if lc_h.dim() == 2:  # the cursor table: left = lcur - segment start
             lc = lc_h[:, 0].to(torch.int64) - offs_cpu[:-1]
