@@ -103,6 +103,15 @@ void forest_oob(torch::Tensor sums, torch::Tensor counts, torch::Tensor x,
                 torch::Tensor mask, int64_t dim, int64_t max_group_nodes);
 std::tuple<int64_t, int64_t, int64_t> forest_oob_geometry();
 
+// csrc/forest_vote.hip
+void forest_vote(torch::Tensor sums, torch::Tensor counts, torch::Tensor x,
+                 torch::Tensor nodes, torch::Tensor table,
+                 torch::Tensor tree_off, torch::Tensor groups,
+                 torch::Tensor mask, int64_t num_classes, bool soft,
+                 bool masked, int64_t max_group_nodes);
+std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>
+forest_vote_geometry();
+
 // csrc/forest_permute.hip
 void forest_permute_loss(torch::Tensor out, torch::Tensor partials,
                          torch::Tensor x, torch::Tensor nodes,

@@ -2599,6 +2599,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "out-of-bag leaf sums and counts of a packed forest under a mask");
   m.def("forest_oob_geometry", &forest_oob_geometry,
         "(threads, rows per lane, grid cap) of forest_oob");
+  m.def("forest_vote", &forest_vote,
+        "vote sums (and out-of-bag counts) of a packed 9-32 class forest");
+  m.def("forest_vote_geometry", &forest_vote_geometry,
+        "(threads, rows per lane: hard, soft KP = 12, 16, 24, 32, grid cap) "
+        "of forest_vote");
   m.def("forest_permute_loss", &forest_permute_loss,
         "loss sums of a packed forest with each feature column shuffled");
   m.def("forest_permute_geometry", &forest_permute_geometry,

@@ -156,8 +156,21 @@ def packed_forest_vote(x, models, subspaces, num_features, soft,
         lv = _vote_leaves(m, soft)
         feat = orig_space_features(m, sub, num_features)
         trees.append(dict(t, feature=feat, leaf_value=lv))
+    if _wide_vote(trees):
+        # 9-32 classes: the LDS-staged voting kernel (csrc/forest_vote.hip)
+        out = _ops.forest_vote(x, trees, soft, cache=cache, native_only=True)
+        if out is not None:
+            return out
     w = torch.ones(len(trees), dtype=torch.float32)
     return _ops.forest_predict(x, trees, w, cache=cache)
+
+
+def _wide_vote(trees):
+    """True when a voting forest has the class count ``forest_vote`` serves."""
+    from ..ops import dispatch as _ops
+
+    k = trees[0]["leaf_value"].shape[1]
+    return _ops.VOTE_MIN_CLASSES <= k <= _ops.VOTE_MAX_CLASSES
 
 
 def packed_forest_oob(x, models, subspaces, num_features, inbag, vote=None,
@@ -189,6 +202,11 @@ def packed_forest_oob(x, models, subspaces, num_features, inbag, vote=None,
         if feat is not m._tree["feature"]:
             t = dict(t, feature=feat)
         trees.append(t)
+    if vote is not None and _wide_vote(trees):
+        res = _ops.forest_vote(x, trees, vote == "soft", inbag=inbag,
+                               cache=cache, native_only=True)
+        if res is not None:
+            return res
     return _ops.forest_oob(x, trees, inbag, cache=cache)
 
 

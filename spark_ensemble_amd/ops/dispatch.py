@@ -1366,6 +1366,198 @@ def forest_oob(x, trees, inbag, cache=None):
     return reference.forest_oob(x, trees, inbag)
 
 
+# ---- vote sums of 9-32 class forests (csrc/forest_vote.hip) ---------------
+
+VOTE_MIN_CLASSES = 9    # below: forest_predict2 / forest_oob serve the forest
+VOTE_MAX_CLASSES = 32   # a row's counters are 32 16-bit register fields
+VOTE_MAX_MEMBERS = 65535  # what one 16-bit counter field holds
+
+# what the last forest_vote call did: {"path": "native" | "reference",
+# "mode": "binned" | "raw" | None, "vote": "hard" | "soft", "kp": KP (the
+# soft table width; 32 for hard votes), "rows_per_lane": R, "groups": G}
+last_forest_vote_info: dict = {}
+
+
+def forest_vote_geometry():
+    """``{"threads", "rows_per_lane": {"hard", 12, 16, 24, 32}, "grid_cap"}``
+    of the native ``forest_vote``: a block's row tile is ``threads *
+    rows_per_lane[...]``, keyed by "hard" or by the soft table width KP."""
+    m = _require_hip("forest_vote_geometry")
+    if m is None:
+        raise RuntimeError("forest_vote_geometry needs the HIP extension")
+    th, hard, s12, s16, s24, s32, cap = m.forest_vote_geometry()
+    return {"threads": int(th), "grid_cap": int(cap),
+            "rows_per_lane": {"hard": int(hard), 12: int(s12), 16: int(s16),
+                              24: int(s24), 32: int(s32)}}
+
+
+def _vote_kp(K):
+    """Soft leaf-table width of a K-class forest: the kernel's compile-time
+    widths are 12, 16, 24 and 32."""
+    return 12 if K <= 12 else 16 if K <= 16 else 24 if K <= 24 else 32
+
+
+def _pack_forest_vote(trees, soft, dev):
+    """Pack voting trees (``leaf_value`` ALREADY transformed per node, as
+    ``ensemble.utils._vote_leaves`` does) for ``forest_vote``: the node
+    words and groups of ``_pack_forest``, with other payloads.
+
+    Hard: a leaf's payload is its class id, the argmax of its one-hot row,
+    and there is no leaf tensor.  Soft: a leaf's payload is its row in
+    ``table`` ``[n_leaves, KP]`` f32, the leaf rows in node order zero-padded
+    to KP columns; inner nodes have no row.  Both carry ``node64`` (f32
+    thresholds) and, through ``_pack_forest_binned``, ``node64b`` and the
+    rank structures.  ``fits`` is False, and nothing else is packed, when a
+    tree exceeds the LDS group budget."""
+    sizes = [t["feature"].numel() for t in trees]
+    T = len(trees)
+    K = trees[0]["leaf_value"].shape[1]
+    pack = {"T": T, "K": K, "dev": dev, "soft": bool(soft),
+            "kp": _vote_kp(K) if soft else 32,
+            "fits": max(sizes) <= _FP2_GROUP_NODES}
+    if not pack["fits"]:
+        return pack
+    feats = torch.cat([t["feature"].to(dev, torch.int32) for t in trees])
+    thrs = torch.cat([t["threshold"].to(dev, torch.float32) for t in trees])
+    lefts = torch.cat([t["left_child"].to(dev, torch.int32) for t in trees])
+    leaves = torch.cat([t["leaf_value"].to(dev, torch.float32) for t in trees])
+    is_leaf = feats < 0
+    if soft:
+        ids = (is_leaf.to(torch.int32).cumsum(0) - 1).to(torch.int32)
+        table = torch.zeros(int(is_leaf.sum()), pack["kp"],
+                            dtype=torch.float32, device=dev)
+        table[:, :K] = leaves[is_leaf]
+        pack["table"] = table.contiguous()
+    else:
+        ids = leaves.argmax(dim=1).to(torch.int32)
+        pack["table"] = torch.empty(0, dtype=torch.float32, device=dev)
+    # integer select: the payload bits of a leaf are an index, not a float
+    payload = torch.where(is_leaf, ids, thrs.view(torch.int32)).view(
+        torch.float32)
+    offsets = torch.tensor([0] + sizes[:-1], dtype=torch.int64).cumsum(0)
+    pack.update(
+        feats=feats, lefts=lefts, f_max=int(feats.max()),
+        offsets32=offsets.to(torch.int32).to(dev),
+        node64=(
+            (feats.to(torch.int64) & 0xFFFF)
+            | ((lefts.to(torch.int64) & 0xFFFF) << 16)
+            | ((payload.view(torch.int32).to(torch.int64) & 0xFFFFFFFF) << 32)
+        ).contiguous())
+
+    # greedy contiguous tree groups under the LDS node budget
+    groups, off_list = [], offsets.tolist()
+    first = acc = 0
+    for t in range(T):
+        if acc + sizes[t] > _FP2_GROUP_NODES and acc > 0:
+            groups.append([first, t - first, off_list[first], acc])
+            first, acc = t, 0
+        acc += sizes[t]
+    groups.append([first, T - first, off_list[first], acc])
+    pack.update(
+        groups_t=torch.tensor(groups, dtype=torch.int32, device=dev),
+        max_nodes=max(g[3] for g in groups))
+    _pack_forest_binned(pack, feats, thrs, payload)
+    return pack
+
+
+def forest_vote(x, trees, soft, inbag=None, cache=None, native_only=False):
+    """Vote sums ``[N, K]`` f32 of a K-class voting forest: member t adds
+    its leaf's row to the row's sums, members in order.  With ``inbag``
+    (``[N, T]`` bool, True: row i was in tree t's bag) only the members
+    that left the row out are summed and the result is ``(sums, counts
+    [N] int32)``, the semantics of ``reference.forest_oob``.
+
+    ``trees`` carry leaves ALREADY transformed per node, as
+    ``ensemble.utils._vote_leaves`` makes and caches them: one-hot argmax
+    rows for hard votes (``soft=False``), normalised probability rows for
+    soft ones.  The packer reads class ids (hard) or the compact leaf table
+    (soft) from them, and the declined route uses them as they are.
+
+    The native pass (csrc/forest_vote.hip) serves CUDA f32 rows,
+    ``9 <= K <= 32``, every tree within ``_FP2_GROUP_NODES``,
+    ``1 <= F < 32768``, ``T <= 65535`` and ``N >= 1``.  Anything else
+    returns what ``forest_predict`` / ``forest_oob`` return (or None under
+    ``native_only``); ``SEA_VOTE_WIDE=0`` forces that route.  Hard sums
+    are exact integers; soft sums are f32 adds in member order, bitwise
+    those of the declined route.  Rows are read as u8 ranks whenever the
+    pack has them, else as f32 (``forest_oob``'s rule);
+    ``SEA_VOTE_MODE=raw|binned`` overrides.  Both are exact.
+
+    ``cache``: caller-owned dict; the pack is kept under "vote_pack", a
+    key no other forest op reads.  Keep one dict per voting strategy."""
+    if not trees:
+        raise ValueError("forest_vote needs at least one tree")
+    N, F = x.shape
+    T = len(trees)
+    K = trees[0]["leaf_value"].shape[1]
+    vote = "soft" if soft else "hard"
+    if inbag is not None:
+        inbag = torch.as_tensor(inbag)
+        if inbag.dim() != 2 or tuple(inbag.shape) != (N, T):
+            raise ValueError(
+                f"inbag is {tuple(inbag.shape)}, expected ({N}, {T})")
+    native = (x.is_cuda and x.dtype == torch.float32 and N >= 1
+              and VOTE_MIN_CLASSES <= K <= VOTE_MAX_CLASSES
+              and 1 <= F < 32768 and T <= VOTE_MAX_MEMBERS
+              and os.environ.get("SEA_VOTE_WIDE") != "0")
+    m = _require_hip("forest_vote") if native else None
+    if m is not None:
+        pack = cache.get("vote_pack") if cache is not None else None
+        if (pack is None or pack["T"] != T or pack["dev"] != x.device
+                or pack["soft"] != bool(soft) or pack["K"] != K):
+            pack = _pack_forest_vote(trees, soft, x.device)
+            if cache is not None:
+                cache["vote_pack"] = pack
+        if pack["fits"]:
+            if pack["f_max"] >= F:
+                raise ValueError(
+                    f"forest splits on feature {pack['f_max']} but x has "
+                    f"{F} columns")
+            binned_avail = bool(
+                pack.get("binned_ok") and pack["bin_fmax"] <= F)
+            env_mode = os.environ.get("SEA_VOTE_MODE")
+            mode = "raw"
+            if binned_avail and env_mode != "raw":
+                mode = "binned"
+            elif env_mode == "binned":
+                raise ValueError(
+                    "SEA_VOTE_MODE=binned: this forest has no u8 rank form "
+                    "(a feature with more than 255 thresholds, or no split "
+                    "at all)")
+            xc = x.contiguous()
+            if mode == "binned":
+                nodes = pack["node64b"]
+                xb = torch.empty(xc.shape, dtype=torch.uint8, device=x.device)
+                m.bin_features(xb, xc, _binned_edges(pack, F))
+                xc = xb
+            else:
+                nodes = pack["node64"]
+            sums = torch.empty(N, K, dtype=torch.float32, device=x.device)
+            if inbag is not None:
+                mask = _pack_inbag(inbag.to(x.device, torch.bool))
+                counts = torch.empty(N, dtype=torch.int32, device=x.device)
+            else:
+                mask = counts = torch.empty(0, dtype=torch.int32,
+                                            device=x.device)
+            groups = pack["groups_t"]
+            m.forest_vote(sums, counts, xc, nodes, pack["table"],
+                          pack["offsets32"], groups, mask, K, bool(soft),
+                          inbag is not None, int(pack["max_nodes"]))
+            rpl = forest_vote_geometry()["rows_per_lane"]
+            last_forest_vote_info.update(
+                path="native", mode=mode, vote=vote, kp=pack["kp"],
+                rows_per_lane=rpl[pack["kp"] if soft else "hard"],
+                groups=int(groups.shape[0]))
+            return sums if inbag is None else (sums, counts)
+    last_forest_vote_info.update(path="reference", mode=None, vote=vote,
+                                 kp=0, rows_per_lane=0, groups=0)
+    if native_only:
+        return None
+    if inbag is None:
+        return forest_predict(x, trees, None, cache=cache)
+    return forest_oob(x, trees, inbag, cache=cache)
+
+
 # ---- permutation loss sums (csrc/forest_permute.hip) ----------------------
 
 # what the last forest_permute_loss call did: {"path": "native" |
