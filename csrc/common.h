@@ -112,6 +112,13 @@ void forest_vote(torch::Tensor sums, torch::Tensor counts, torch::Tensor x,
 std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>
 forest_vote_geometry();
 
+// csrc/forest_margin.hip
+void forest_margin(torch::Tensor out, torch::Tensor x, torch::Tensor nodes,
+                   torch::Tensor tree_off, torch::Tensor tree_plane,
+                   torch::Tensor groups, int64_t num_planes,
+                   int64_t max_group_nodes);
+std::tuple<int64_t, int64_t, int64_t> forest_margin_geometry();
+
 // csrc/forest_permute.hip
 void forest_permute_loss(torch::Tensor out, torch::Tensor partials,
                          torch::Tensor x, torch::Tensor nodes,

@@ -2604,6 +2604,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("forest_vote_geometry", &forest_vote_geometry,
         "(threads, rows per lane: hard, soft KP = 12, 16, 24, 32, grid cap) "
         "of forest_vote");
+  m.def("forest_margin", &forest_margin,
+        "margins [N, planes] of a plane-major packed forest of scalar trees");
+  m.def("forest_margin_geometry", &forest_margin_geometry,
+        "(threads, rows per lane, grid cap) of forest_margin");
   m.def("forest_permute_loss", &forest_permute_loss,
         "loss sums of a packed forest with each feature column shuffled");
   m.def("forest_permute_geometry", &forest_permute_geometry,

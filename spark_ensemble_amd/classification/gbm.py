@@ -569,9 +569,19 @@ class GBMClassificationModel(ProbabilisticClassificationModel, _GBMClassifierPar
         return get_classification_loss(self.getLoss(), self._num_classes)
 
     def _margins(self, x: torch.Tensor) -> torch.Tensor:
-        from ..ensemble.utils import packed_forest_margin
+        from ..ensemble.utils import packed_forest_margin, packed_forest_margins
 
         out = self._init.predictRaw(x)[:, : self._dim].contiguous()
+        if self._models and self._dim >= 2:
+            # tree stages, any subspaces, narrow inputs: every class dimension
+            # in one plane-routed forest walk over one pack
+            # (csrc/forest_margin.hip); None sends the model class by class
+            sums = packed_forest_margins(
+                x, self._models, self._weights, self._subspaces, x.shape[1],
+                cache=self.__dict__.setdefault("_margin_cache", {}),
+            )
+            if sums is not None:
+                return out + sums
         if self._models:
             # fast path: identity subspaces + tree stages -> one packed
             # forest_predict kernel per class dimension (arena cached

@@ -117,6 +117,54 @@ def packed_forest_margin(x, models, weights, subspaces, num_features,
     return _ops.forest_predict(x, trees, w, cache=cache).squeeze(1)
 
 
+# forest_margin reads rows row-major; the per-class route also has a
+# transposed u8 form, which its probe picks for wide rows.  Measured on an
+# MI355X (profiles/forest_margin.md): at 16 features the one-launch walk is
+# level with the per-class route or ahead of it, from 64 features on it is
+# behind (3.9x at 2M x 256 rows, 100 stages of depth 8).  Wider inputs
+# therefore keep the per-class route unless SEA_MARGIN_FUSED=1.
+MARGIN_FUSED_MAX_FEATURES = 16
+
+
+def packed_forest_margins(x, models, weights, subspaces, num_features,
+                          cache=None):
+    """All margin columns of a multi-dimensional boosted ensemble as ONE
+    ``forest_margin`` call (csrc/forest_margin.hip): ``models[s][j]`` adds
+    ``weights[s][j]`` times its prediction to column j, ``subspaces[s]`` is
+    stage s's.  ``packed_forest_margin``'s contract otherwise: built-in
+    regression trees only, subspaced stages walk the unsliced x through the
+    ``_tree_orig_feats`` remap.  Returns ``[N, dim]`` f32 sums (init margins
+    not included), or None when a stage is not such a tree, the op would
+    not run its kernel, or x has more than ``MARGIN_FUSED_MAX_FEATURES``
+    columns (``SEA_MARGIN_FUSED=1`` lifts that); the caller then serves
+    class by class."""
+    import os
+
+    from ..models.tree import DecisionTreeRegressionModel
+    from ..ops import dispatch as _ops
+
+    if not models:
+        return None
+    if (num_features > MARGIN_FUSED_MAX_FEATURES
+            and os.environ.get("SEA_MARGIN_FUSED") != "1"):
+        return None
+    dim = len(models[0])
+    trees, w, planes = [], [], []
+    for ms, wts, sub in zip(models, weights, subspaces):
+        for j, m in enumerate(ms):
+            if not isinstance(m, DecisionTreeRegressionModel):
+                return None
+            t = m._tree
+            feat = orig_space_features(m, sub, num_features)
+            if feat is not t["feature"]:
+                t = dict(t, feature=feat)
+            trees.append(t)
+            w.append(float(wts[j]))
+            planes.append(j)
+    return _ops.forest_margin(x, trees, w, planes, dim, cache=cache,
+                              native_only=True)
+
+
 def _vote_leaves(m, soft):
     """Per-node leaf transform of a classification tree under voting
     (cached on the model): normalized probabilities for soft voting, the

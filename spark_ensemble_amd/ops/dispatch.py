@@ -1558,6 +1558,176 @@ def forest_vote(x, trees, soft, inbag=None, cache=None, native_only=False):
     return forest_oob(x, trees, inbag, cache=cache)
 
 
+# ---- margins of a multi-plane boosted forest (csrc/forest_margin.hip) -----
+
+# what the last forest_margin call did: {"path": "native" | "reference",
+# "mode": "binned" | "raw" | None, "rows_per_lane": R, "groups": G,
+# "planes": P}
+last_forest_margin_info: dict = {}
+
+
+def forest_margin_geometry():
+    """``{"threads", "rows_per_lane", "grid_cap"}`` of the native
+    ``forest_margin``: a block's row tile is ``threads * rows_per_lane``."""
+    m = _require_hip("forest_margin_geometry")
+    if m is None:
+        raise RuntimeError("forest_margin_geometry needs the HIP extension")
+    th, rows, cap = m.forest_margin_geometry()
+    return {"threads": int(th), "rows_per_lane": int(rows),
+            "grid_cap": int(cap)}
+
+
+def _pack_forest_margin(trees, weights, planes, dev):
+    """Pack scalar-leaf trees PLANE-MAJOR for ``forest_margin``: ``order`` is
+    the stable sort of the tree indices by plane (stage order survives inside
+    a plane) and every tensor below is in that order.  The node words and
+    groups are those of ``_pack_forest`` at ``D == 1`` (a leaf's payload is
+    the f32 bits of ``weight * leaf``); ``planes_t`` is the per-tree int32
+    plane table beside ``offsets32``.  ``fits`` is False, and nothing else is
+    packed, when a tree exceeds the LDS group budget."""
+    T = len(trees)
+    order = sorted(range(T), key=planes.__getitem__)  # stable
+    trees = [trees[i] for i in order]
+    sizes = [t["feature"].numel() for t in trees]
+    pack = {"T": T, "dev": dev, "order": order,
+            "fits": max(sizes) <= _FP2_GROUP_NODES}
+    if not pack["fits"]:
+        return pack
+    feats = torch.cat([t["feature"].to(dev, torch.int32) for t in trees])
+    thrs = torch.cat([t["threshold"].to(dev, torch.float32) for t in trees])
+    lefts = torch.cat([t["left_child"].to(dev, torch.int32) for t in trees])
+    leaves = torch.cat([t["leaf_value"].to(dev, torch.float32) for t in trees])
+    w = torch.as_tensor(weights, dtype=torch.float32)[order].to(dev)
+    tree_id = torch.repeat_interleave(
+        torch.arange(T, device=dev), torch.tensor(sizes, device=dev))
+    payload = torch.where(feats < 0, w[tree_id] * leaves[:, 0], thrs)
+    offsets = torch.tensor([0] + sizes[:-1], dtype=torch.int64).cumsum(0)
+    pack.update(
+        feats=feats, lefts=lefts, f_max=int(feats.max()),
+        offsets32=offsets.to(torch.int32).to(dev),
+        planes_t=torch.tensor([planes[i] for i in order], dtype=torch.int32,
+                              device=dev),
+        node64=(
+            (feats.to(torch.int64) & 0xFFFF)
+            | ((lefts.to(torch.int64) & 0xFFFF) << 16)
+            | ((payload.view(torch.int32).to(torch.int64) & 0xFFFFFFFF) << 32)
+        ).contiguous())
+
+    # greedy contiguous tree groups under the LDS node budget
+    groups, off_list = [], offsets.tolist()
+    first = acc = 0
+    for t in range(T):
+        if acc + sizes[t] > _FP2_GROUP_NODES and acc > 0:
+            groups.append([first, t - first, off_list[first], acc])
+            first, acc = t, 0
+        acc += sizes[t]
+    groups.append([first, T - first, off_list[first], acc])
+    pack.update(
+        groups_t=torch.tensor(groups, dtype=torch.int32, device=dev),
+        max_nodes=max(g[3] for g in groups))
+    _pack_forest_binned(pack, feats, thrs, payload)
+    return pack
+
+
+def forest_margin(x, trees, weights, planes, num_planes, cache=None,
+                  native_only=False):
+    """Margins ``[N, num_planes]`` f32 of a forest of scalar-leaf trees: tree
+    t adds ``weights[t] * leaf`` to column ``planes[t]``, the trees of a
+    plane in the order given.  A K-class GBM is ``stages * K`` such trees
+    with ``planes[t] = t % K``.  A plane without trees is legal and stays 0.
+
+    The native pass (csrc/forest_margin.hip) walks all planes in ONE launch
+    over ONE plane-major pack: CUDA f32 rows, ``N >= 1``, ``num_planes >= 2``,
+    every tree within ``_FP2_GROUP_NODES`` and ``1 <= F < 32768``.  Anything
+    else returns the per-plane composition of ``forest_predict`` (or None
+    under ``native_only``); ``SEA_MARGIN_FUSED=0`` forces that route.  Every
+    element is an f32 sum in the given order: reproducible bit for bit.  Rows
+    are read as u8 ranks whenever the pack has them, else as f32
+    (``forest_vote``'s rule); ``SEA_MARGIN_MODE=raw|binned`` overrides.  Both
+    are exact.
+
+    ``cache``: caller-owned dict; the pack is kept under "margin_pack", a
+    key no other forest op reads (the declined route keeps its per-plane
+    packs under "plane_caches")."""
+    if not trees:
+        raise ValueError("forest_margin needs at least one tree")
+    N, F = x.shape
+    T = len(trees)
+    P = int(num_planes)
+    planes = [int(p) for p in planes]
+    if len(planes) != T or len(weights) != T:
+        raise ValueError(
+            f"{T} trees need {T} weights and planes, got {len(weights)} "
+            f"and {len(planes)}")
+    if min(planes) < 0 or max(planes) >= P:
+        raise ValueError(f"planes must lie in [0, {P})")
+    if any(t["leaf_value"].shape[1] != 1 for t in trees):
+        raise ValueError("forest_margin needs scalar-leaf trees")
+    native = (x.is_cuda and x.dtype == torch.float32 and N >= 1 and P >= 2
+              and 1 <= F < 32768
+              and os.environ.get("SEA_MARGIN_FUSED") != "0")
+    m = _require_hip("forest_margin") if native else None
+    if m is not None:
+        pack = cache.get("margin_pack") if cache is not None else None
+        if pack is None or pack["T"] != T or pack["dev"] != x.device:
+            pack = _pack_forest_margin(trees, weights, planes, x.device)
+            if cache is not None:
+                cache["margin_pack"] = pack
+        if pack["fits"]:
+            if pack["f_max"] >= F:
+                raise ValueError(
+                    f"forest splits on feature {pack['f_max']} but x has "
+                    f"{F} columns")
+            binned_avail = bool(
+                pack.get("binned_ok") and pack["bin_fmax"] <= F)
+            env_mode = os.environ.get("SEA_MARGIN_MODE")
+            mode = "raw"
+            if binned_avail and env_mode != "raw":
+                mode = "binned"
+            elif env_mode == "binned":
+                raise ValueError(
+                    "SEA_MARGIN_MODE=binned: this forest has no u8 rank form "
+                    "(a feature with more than 255 thresholds, or no split "
+                    "at all)")
+            xc = x.contiguous()
+            if mode == "binned":
+                nodes = pack["node64b"]
+                xb = torch.empty(xc.shape, dtype=torch.uint8, device=x.device)
+                m.bin_features(xb, xc, _binned_edges(pack, F))
+                xc = xb
+            else:
+                nodes = pack["node64"]
+            # the kernel stores a plane when it leaves it: one that no tree
+            # names is never stored
+            alloc = torch.empty if len(set(planes)) == P else torch.zeros
+            out = alloc(N, P, dtype=torch.float32, device=x.device)
+            groups = pack["groups_t"]
+            m.forest_margin(out, xc, nodes, pack["offsets32"],
+                            pack["planes_t"], groups, P,
+                            int(pack["max_nodes"]))
+            last_forest_margin_info.update(
+                path="native", mode=mode,
+                rows_per_lane=forest_margin_geometry()["rows_per_lane"],
+                groups=int(groups.shape[0]), planes=P)
+            return out
+    last_forest_margin_info.update(path="reference", mode=None,
+                                   rows_per_lane=0, groups=0, planes=P)
+    if native_only:
+        return None
+    if not x.is_cuda:
+        return reference.forest_margin(x, trees, weights, planes, P)
+    w = torch.as_tensor(weights, dtype=torch.float32)
+    caches = cache.setdefault("plane_caches", {}) if cache is not None else {}
+    out = torch.zeros(N, P, dtype=torch.float32, device=x.device)
+    for j in range(P):
+        idx = [t for t in range(T) if planes[t] == j]
+        if idx:
+            out[:, j] = forest_predict(
+                x, [trees[t] for t in idx], w[idx],
+                cache=caches.setdefault(j, {}))[:, 0]
+    return out
+
+
 # ---- permutation loss sums (csrc/forest_permute.hip) ----------------------
 
 # what the last forest_permute_loss call did: {"path": "native" |

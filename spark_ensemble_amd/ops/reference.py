@@ -431,6 +431,22 @@ def forest_predict(
     return out
 
 
+def forest_margin(x, trees, weights, planes, num_planes):
+    """Margins ``[N, num_planes]`` of scalar-leaf trees: column j is the sum,
+    in the order given, of ``weights[t] * tree_t(x)`` over the trees with
+    ``planes[t] == j``; a plane without trees stays 0.  Runs in the dtype
+    of ``x``."""
+    out = torch.zeros(x.shape[0], int(num_planes), dtype=x.dtype,
+                      device=x.device)
+    w = torch.as_tensor(weights, dtype=x.dtype)
+    for j in range(int(num_planes)):
+        idx = [t for t, p in enumerate(planes) if int(p) == j]
+        if idx:
+            out[:, j] = forest_predict(
+                x, [trees[t] for t in idx], w[idx])[:, 0]
+    return out
+
+
 def forest_staged_loss(x, trees, weights, dim, init, label, row_weight, loss):
     """Per-stage loss sums of a boosted forest: ``[S + 1]`` float64.
 

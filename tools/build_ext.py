@@ -32,6 +32,7 @@ SRC = [
     os.path.join(REPO, "csrc", "gbm_round.hip"),
     os.path.join(REPO, "csrc", "goss.hip"),
     os.path.join(REPO, "csrc", "forest_vote.hip"),
+    os.path.join(REPO, "csrc", "forest_margin.hip"),
 ]
 # Sources compiled on their own, with flags the rest is not built with.
 # forest_wquantile.hip: packed f32 instructions (v_pk_add/mul/fma_f32) off.
@@ -55,6 +56,9 @@ SRC = [
 # forest_vote.hip: the same guard; its f32 arithmetic is one add per class and
 # member, in member order, whose bits tests/test_forest_vote_gpu.py compares
 # with the v1 route.
+# forest_margin.hip: the same guard; its f32 arithmetic is one add per tree, in
+# stage order, whose bits tests/test_forest_margin_gpu.py compares with the
+# per-class forest_predict2 route.
 _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SRC_FLAGS = {
     "forest_wquantile.hip": _NO_PACKED_F32,
@@ -63,6 +67,7 @@ SRC_FLAGS = {
     "gbm_round.hip": _NO_PACKED_F32,
     "goss.hip": _NO_PACKED_F32,
     "forest_vote.hip": _NO_PACKED_F32,
+    "forest_margin.hip": _NO_PACKED_F32,
 }
 OUT = os.path.join(REPO, "spark_ensemble_amd", "_hip_ops.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
